@@ -20,8 +20,11 @@ single core and all usable cores) and two parity objects over the whole batch.
 Output (round 5): the DETAILED record goes to a file (`--detail-out`, default gpurun_out/bench_detail.json) and to stderr on one line prefixed
 `DETAIL `; stdout carries exactly ONE line, printed last: the compact contract line built by `contract_line()` (< 4 KB — a CPU test pins the
 size), which is what the driver parses. The timed region is a BLOCK of exactly `--steps` steps bracketed by barrier + synchronize on both
-sides; the block is repeated until at least `--min-seconds` of timed work have run and the MEDIAN block (max over ranks per block) is reported,
-so that a 20-step block of 23 ms is not the only evidence of a 48 s run.
+sides; by default it runs once, so `--steps` is the number of timed steps. `--min-seconds S` repeats the block until at least S seconds of
+timed work have run and reports the MEDIAN block (max over ranks per block).
+
+`--dump-outputs DIR` writes, after the timed steps, what the last timed step returned (x, lam and the per-instance info fields) as
+DIR/<name>.npy, so that two builds run with the same arguments (hence the same seeded inputs) can be compared output for output.
 """
 import argparse
 import json
@@ -155,6 +158,27 @@ def contract_line(out, detail_path=None):
     return line
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, seed, budget=DUMP_BUDGET_BYTES, prefix="", first=0):
+    """Write `arrays` (name -> per-instance array, first axis = instance) as out_dir/<prefix><name>.npy in float64. If they exceed `budget`
+    bytes, a fixed seeded sample of instances is written instead (the same rows for every array); `<prefix>instance.npy` always holds the
+    indices of the instances written in the workload's instance stream (`first` = index of row 0), so two runs with the same arguments can be compared output for output."""
+    import numpy as np
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    B = len(next(iter(arrays.values())))
+    assert all(len(v) == B for v in arrays.values())
+    row_bytes = 8 * (1 + sum(int(np.prod(v.shape[1:])) for v in arrays.values()))
+    keep = max(1, min(B, budget // row_bytes))
+    rows = np.arange(B) if keep == B else np.sort(np.random.default_rng(seed).choice(B, keep, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, prefix + "instance.npy"), (first + rows).astype(np.float64))
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, prefix + k + ".npy"), np.ascontiguousarray(v[rows]))
+    return rows
+
+
 def usable_cpus():
     """Host threads this process may really use: the affinity mask, capped by the cgroup CPU quota (a container can report 256
     CPUs and be allowed 16 of them)."""
@@ -187,12 +211,16 @@ def main():
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="minimum wall time of the all-core CPU-baseline sample (single core: half)")
     ap.add_argument("--configs", default="B,C,D,R,P", help="sub-records beside the headline (N = 1 only): any of B, C, D (BASELINE.json configs[2..4]) R (the reference's own 16-node robot grid, 128 KKT rows) and P (the problems of the reference's two NP = 1 control tests as batches); '' = none")
     ap.add_argument("--no-replay", action="store_true", help="skip the QP-only replay record")
-    ap.add_argument("--min-seconds", type=float, default=2.0, help="repeat the timed block of --steps steps until this much timed work has run; the median block is reported (0 = one block)")
+    ap.add_argument("--min-seconds", type=float, default=0.0, help="0 (default): one timed block of exactly --steps steps. S > 0: repeat that block until S seconds of timed work "
+                    "have run and report the median block")
     ap.add_argument("--max-blocks", type=int, default=400)
     ap.add_argument("--detail-out", default=os.path.join("gpurun_out", "bench_detail.json"), help="file for the detailed record (rank 0); '' = stderr only")
     ap.add_argument("--streams", type=int, default=1, help="1 (default, the contract's configuration): every step is one launch on one "
                     "stream. S > 1: consecutive steps alternate over S contexts (own stream, workspace and output buffers), so that a "
                     "step's tail overlaps the next step's start — a pipelined-server figure, reported in DESIGN.md, not the bench line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write what the last timed step returned (x, lam and "
+                    "the per-instance info fields) as DIR/<name>.npy in float64, at most 64 MB (a seeded sample of instances beyond that); "
+                    "with N > 1 ranks every rank writes its own shard as DIR/rank<r>_<name>.npy")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
@@ -291,6 +319,12 @@ def main():
     step_ms = np.array(block_ms[med])                                 # HIP events on the launch stream: one kernel launch per step
     kernel_ms = float(np.mean(step_ms))                               # average launch duration over the MEDIAN block's steps: the dominant kernel cannot exceed the step it is part of (kernel_ms <= ms_per_step)
     kernel_ms_all_blocks = float(np.mean([np.mean(b) for b in block_ms]))   # the same average over every timed block (what rocprofv3 --stats averages; carries the slow blocks of a noisy box)
+
+    last_x, last_lam, last_info = outs[(counter[0] - 1) % S_]          # the buffers the last timed step wrote
+    if args.dump_outputs:
+        linfo = np.frombuffer(last_info.cpu().numpy().tobytes(), dtype=pa.capi.SQP_INFO_DTYPE)
+        dump_outputs(args.dump_outputs, {"x": last_x.cpu().numpy(), "lam": last_lam.cpu().numpy(), **{"info_" + f: linfo[f] for f in linfo.dtype.names}},
+                     workloads.SEED, DUMP_BUDGET_BYTES // world, "rank%d_" % rank if world > 1 else "", sharding.shard_first_instance(rank, B))
 
     info = np.frombuffer(d_info.cpu().numpy().tobytes(), dtype=pa.capi.SQP_INFO_DTYPE)
     qp_solves = int(info["iter"].sum())

@@ -2,7 +2,9 @@
 oracle/Makefile from /root/reference/tests/solvers/sqp/casadi_codegen/*.cpp — the reference's CasADi-generated C for
 the 11-node (P=5, S=2) mobile-robot NLP: 55 variables, 33 equality constraints, t in [0,1], wheel base 1, Q=R=I,
 Mayer x'x).  Run in the build container (needs /root/reference):  python tests/golden/make_golden.py
-Output: tests/golden/casadi_robot_P5S2.npz  (inputs + expected outputs only; no reference source)."""
+Output: tests/golden/casadi_robot_P5S2.npz  (inputs + expected outputs only; no reference source), and
+        tests/golden/casadi_robot_P5S2_rng3.npz (the point of test_oracle_pins.py::test_collocation_against_live_reference_build, which
+        that test checks against when oracle/_ref is not built)."""
 import os
 import sys
 
@@ -33,3 +35,6 @@ for x, lam in zip(pts, lams):
     out["lag_hess"].append(r._dense("flagrangian_hessian", r._call("flagrangian_hessian", [x, lam], [r.nnz("flagrangian_hessian")])[0]))
 np.savez_compressed(os.path.join(os.path.dirname(__file__), "casadi_robot_P5S2.npz"), **{k: np.array(v) for k, v in out.items()})
 print("wrote casadi_robot_P5S2.npz with", len(pts), "points")
+x3 = np.random.default_rng(3).uniform(-2, 2, 55)
+np.savez_compressed(os.path.join(os.path.dirname(__file__), "casadi_robot_P5S2_rng3.npz"), x=x3, cost=r.cost(x3), c=r.constraint(x3))
+print("wrote casadi_robot_P5S2_rng3.npz")

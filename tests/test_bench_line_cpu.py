@@ -92,3 +92,25 @@ def test_round6_record_is_consistent_and_carries_the_new_keys():
         assert rec["route"] == rec["lone_instance_route"] == "condreg" and rec["batch"] == 4096 and 0 < rec["lone_instance_ms"] < rec["ms_per_batch"]["median"]
         assert rec["parity"]["bit_identical_x"] and rec["parity"]["bit_identical_lam"] and rec["parity"]["identical_trajectory_fraction_vs_reference_order"] == 1.0
     assert set(line["reference_tests"]) == set(rt) and all(v[2] == "condreg" and v[3] is True for v in line["reference_tests"].values())
+
+
+def test_dump_outputs_is_float64_bounded_and_deterministic(tmp_path):
+    """--dump-outputs: every file is float64 with the instances on the first axis; past the byte budget the same seeded instance sample is written
+    on every run, and instance.npy names the instances written."""
+    import numpy as np
+    import bench
+    B = 1000
+    arrays = {"x": np.arange(B * 5, dtype=np.float64).reshape(B, 5), "info_iter": np.arange(B, dtype=np.int32)}
+    rows = bench.dump_outputs(str(tmp_path / "all"), arrays, 7, first=4096)
+    assert np.array_equal(rows, np.arange(B))
+    assert np.array_equal(np.load(tmp_path / "all" / "x.npy"), arrays["x"]) and np.load(tmp_path / "all" / "info_iter.npy").dtype == np.float64
+    assert np.array_equal(np.load(tmp_path / "all" / "instance.npy"), 4096 + np.arange(B))
+    budget = 8 * 7 * 100   # (instance, 5 x values, iter) per row: room for exactly 100 rows
+    r1 = bench.dump_outputs(str(tmp_path / "a"), arrays, 7, budget=budget)
+    r2 = bench.dump_outputs(str(tmp_path / "b"), arrays, 7, budget=budget)
+    assert len(r1) == 100 and np.array_equal(r1, r2) and np.all(np.diff(r1) > 0)
+    for d in ("a", "b"):
+        files = sorted(os.listdir(tmp_path / d))
+        assert files == ["info_iter.npy", "instance.npy", "x.npy"]
+        assert sum(np.load(tmp_path / d / f).nbytes for f in files) <= budget
+        assert np.array_equal(np.load(tmp_path / d / "x.npy"), arrays["x"][r1])

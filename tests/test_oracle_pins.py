@@ -68,13 +68,19 @@ def test_collocation_against_reference_golden(oracle):
 
 
 def test_collocation_against_live_reference_build(oracle):
-    if not os.path.exists(oracle.REF_PATH):
-        pytest.skip("oracle/_ref not built (reference tree absent)")
-    r = oracle.RefCasadiRobot()
+    """Against the reference's fixtures built into oracle/_ref when they are there, and always against the values they gave at the same point
+    (tests/golden/casadi_robot_P5S2_rng3.npz, written by tests/golden/make_golden.py)."""
     x = np.random.default_rng(3).uniform(-2, 2, 55)
+    g = np.load(os.path.join(os.path.dirname(__file__), "golden", "casadi_robot_P5S2_rng3.npz"))
+    assert np.array_equal(g["x"], x)
+    expected = [(float(g["cost"]), g["c"])]
+    if os.path.exists(oracle.REF_PATH):
+        r = oracle.RefCasadiRobot()
+        expected.append((r.cost(x), r.constraint(x)))
     ev = oracle.ocp_eval(oracle.MODEL_ROBOT, 5, 2, 0.0, 1.0, x, [1.0])
-    assert abs(ev["cost"] - r.cost(x)) < 1e-13
-    assert np.abs(ev["c"] - r.constraint(x)).max() < 1e-13
+    for cost, c in expected:
+        assert abs(ev["cost"] - cost) < 1e-13
+        assert np.abs(ev["c"] - c).max() < 1e-13
 
 
 def test_dense_layout_parking_np1(oracle):
