@@ -10,34 +10,14 @@
 namespace pmpc {
 
 template <class Model>
-bool try_launch_extra_grids(pmpc_context* ctx, const Model& mdl, const ChebData* cd, int P, int S, int B, const double* x_guess,
-                            const double* lam_guess, const double* d, const double* lbx, const double* ubx, const double* lbg,
-                            const double* ubg, const pmpc_sqp_settings* ss, const pmpc_qp_settings* qs, double* Hws, double* Aws, double* x,
-                            double* lam, pmpc_sqp_info* info, hipStream_t stream, size_t lds_limit, unsigned long long* phase, pmpc_status* st,
-                            double* slice_state, int slice_iters) {
-#define PMPC_TRY_GRID(NNODES_)                                                                                                                       \
-    if (try_launch_reg<Model, NNODES_, true>(ctx, mdl, cd, P, S, B, x_guess, lam_guess, d, lbx, ubx, lbg, ubg, ss, qs, Hws, Aws, x, lam, info, stream, \
-                                             lds_limit, phase, st, slice_state, slice_iters))                                                         \
-        return true;
-    PMPC_TRY_GRID(3)
-    PMPC_TRY_GRID(4)
-    PMPC_TRY_GRID(6)
-    PMPC_TRY_GRID(8)
-    PMPC_TRY_GRID(9)
-    PMPC_TRY_GRID(10)
-    PMPC_TRY_GRID(12)
-    PMPC_TRY_GRID(13)
-    PMPC_TRY_GRID(14)
-    PMPC_TRY_GRID(15)   // 113..128 rows where the model fits them (robot: 15 and 16 nodes — the reference's mpc_wrapper_test grid; CSTR: 12 above)
-    PMPC_TRY_GRID(16)
-#undef PMPC_TRY_GRID
-    return false;
+bool plan_extra_grids(pmpc_context* ctx, const SqpArgs<Model>& a, SqpPlan<Model>& p) {
+    return plan_reg<Model, 3, true>(ctx, a, p) || plan_reg<Model, 4, true>(ctx, a, p) || plan_reg<Model, 6, true>(ctx, a, p) ||
+           plan_reg<Model, 8, true>(ctx, a, p) || plan_reg<Model, 9, true>(ctx, a, p) || plan_reg<Model, 10, true>(ctx, a, p) ||
+           plan_reg<Model, 12, true>(ctx, a, p) || plan_reg<Model, 13, true>(ctx, a, p) || plan_reg<Model, 14, true>(ctx, a, p) ||
+           plan_reg<Model, 15, true>(ctx, a, p) || plan_reg<Model, 16, true>(ctx, a, p);   // 15, 16: 113..128 rows where the model fits them (robot: 15 and 16 nodes — the reference's mpc_wrapper_test grid; CSTR: 12 above)
 }
 
 }  // namespace pmpc
 
-#define PMPC_INSTANTIATE_GRIDS(MODEL)                                                                                                                 \
-    template bool pmpc::try_launch_extra_grids<MODEL>(pmpc_context*, const MODEL&, const pmpc::ChebData*, int, int, int, const double*, const double*,  \
-                                                      const double*, const double*, const double*, const double*, const double*,                       \
-                                                      const pmpc_sqp_settings*, const pmpc_qp_settings*, double*, double*, double*, double*,            \
-                                                      pmpc_sqp_info*, hipStream_t, size_t, unsigned long long*, pmpc_status*, double*, int);
+#define PMPC_INSTANTIATE_GRIDS(MODEL) \
+    template bool pmpc::plan_extra_grids<MODEL>(pmpc_context*, const pmpc::SqpArgs<MODEL>&, pmpc::SqpPlan<MODEL>&);

@@ -321,29 +321,44 @@ inline bool schur_request_ok(const pmpc_sqp_settings* ss, const pmpc_qp_settings
     return (ss->hessian_update == 1 || ss->exact_hessian_every_iter) && (ss->regularisation == 0 || ss->regularisation == 2) && ss->preconditioner == 0 &&
            ss->qp_solver == 0 && (ss->kkt_form == 0 || ss->kkt_form == 2) && qs->linear_solver == 0 && slice_iters == 0;   // (line_search = 1: the grids compiled with the hook, try_launch_schur)
 }
+// The per-call arguments of a fused SQP launch (device buffers, settings, context services), passed by const reference to the launch helpers;
+// the kernels still take their own by-value arguments
+template <class Model> struct SqpArgs {
+    const Model& mdl; const ChebData* cd; int P, S, B;
+    const double *x_guess, *lam_guess, *d, *lbx, *ubx, *lbg, *ubg;
+    double *x, *lam; pmpc_sqp_info* info;
+    const pmpc_sqp_settings* ss; const pmpc_qp_settings* qs;
+    double *Hws, *Aws; hipStream_t stream; size_t lds_limit;
+    unsigned long long* phase;   // phase-timer counters (PMPC_PHASE_PROFILE=1), else null
+    double* slice_state; int slice_iters;
+};
+template <class Kernel> inline bool set_lds_attr(Kernel kern, size_t lds) {
+    return hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess;
+}
+inline pmpc_status launch_status() { return (hipGetLastError() == hipSuccess) ? PMPC_OK : PMPC_ERR_HIP; }
+
 template <class Model, int PP, int SS>
-inline bool try_launch_schur(pmpc_context* ctx, const Model& mdl, const ChebData* cd, int P, int S, int B, const double* x_guess, const double* lam_guess,
-                             const double* d, const double* lbx, const double* ubx, const pmpc_sqp_settings* ss, const pmpc_qp_settings* qs, double* x,
-                             double* lam, pmpc_sqp_info* info, hipStream_t stream, size_t lds_limit, unsigned long long* phase, pmpc_status* st) {
-    if (P != PP || S != SS) return false;
+inline bool try_launch_schur(pmpc_context* ctx, const SqpArgs<Model>& a, pmpc_status* st) {
+    if (a.P != PP || a.S != SS) return false;
     // Systems of at most 64 KKT rows stay on the one-row-per-lane dense kernel: its ADMM iteration is ONE register mat-vec (600 cycles), the
     // block-structured one a chain of eight LDS exchanges and two mat-vecs (3.7 k cycles on config A) — measured 1.69 against 1.16 ms per 4096
     // config-A instances although the factorisation is three times cheaper. PMPC_SCHUR_SMALL=1: developer switch.
     if (SchurDims<Model, PP, SS>::N + SchurDims<Model, PP, SS>::M <= WAVE && !pmpc_internal_switch(ctx, PMPC_SW_SCHUR_SMALL)) return false;
-    const size_t lds = sqp_schur_lds_bytes<Model, PP, SS>(ss->line_search == 1);
-    if (lds > lds_limit) return false;
+    const size_t lds = sqp_schur_lds_bytes<Model, PP, SS>(a.ss->line_search == 1);
+    if (lds > a.lds_limit) return false;
+    unsigned long long* phase = a.phase;
     auto kern = sqp_schur_kernel<Model, PP, SS, false>;
     if constexpr (SchurDims<Model, PP, SS>::NPAR == 0) { if (phase) kern = sqp_schur_kernel<Model, PP, SS, true>; }   // (no phase-timer build of the bordered form: a developer switch already)
     else phase = nullptr;
     // the filter line search (round 5): compiled for the grids of the reference's own tests with more than 64 KKT rows (11 and 16 nodes), no phase timers
-    if (ss->line_search == 1) {
+    if (a.ss->line_search == 1) {
         if constexpr (SchurDims<Model, PP, SS>::NPAR == 0 && (SchurDims<Model, PP, SS>::NNODES == 11 || SchurDims<Model, PP, SS>::NNODES == 16)) { kern = sqp_schur_kernel<Model, PP, SS, false, true>; phase = nullptr; }
         else return false;
     }
-    if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) { *st = PMPC_ERR_HIP; return true; }
+    if (!set_lds_attr(kern, lds)) { *st = PMPC_ERR_HIP; return true; }
     pmpc_internal_set_route(ctx, PMPC_ROUTE_SCHUR);
-    hipLaunchKernelGGL(kern, dim3(B), dim3(WAVE), lds, stream, mdl, cd, B, x_guess, lam_guess, d, lbx, ubx, *ss, *qs, x, lam, info, phase);
-    *st = (hipGetLastError() == hipSuccess) ? PMPC_OK : PMPC_ERR_HIP;
+    hipLaunchKernelGGL(kern, dim3(a.B), dim3(WAVE), lds, a.stream, a.mdl, a.cd, a.B, a.x_guess, a.lam_guess, a.d, a.lbx, a.ubx, *a.ss, *a.qs, a.x, a.lam, a.info, phase);
+    *st = launch_status();
     return true;
 }
 // the grids with a block-structured specialisation, per model (defined in the model's own translation unit: pmpc_schur_*.hip)
@@ -351,10 +366,7 @@ template <class Model> struct SCHUR_GRIDS { static constexpr bool value = false;
 template <> struct SCHUR_GRIDS<RobotOCP> { static constexpr bool value = true; };
 template <> struct SCHUR_GRIDS<CstrOCP> { static constexpr bool value = true; };
 template <> struct SCHUR_GRIDS<ParkingOCP> { static constexpr bool value = true; };   // (NP = 1: the bordered form, round 5)
-template <class Model>
-bool try_launch_schur_grids(pmpc_context* ctx, const Model& mdl, const ChebData* cd, int P, int S, int B, const double* x_guess, const double* lam_guess,
-                            const double* d, const double* lbx, const double* ubx, const pmpc_sqp_settings* ss, const pmpc_qp_settings* qs, double* x,
-                            double* lam, pmpc_sqp_info* info, hipStream_t stream, size_t lds_limit, unsigned long long* phase, pmpc_status* st);
+template <class Model> bool try_launch_schur_grids(pmpc_context* ctx, const SqpArgs<Model>& a, pmpc_status* st);
 
 // ---------------------------------------------------------------------------------------------------------------------------------------------
 // Round-robin execution of a batch that exceeds the resident wavefronts (register-resident QP, one KKT row per lane) — a DEVELOPER SWITCH
@@ -547,25 +559,39 @@ __global__ __launch_bounds__(64, PMPC_SQP_WAVES) void sqp_kernel_rr(Model model,
 #undef RR_T
 #undef RR_ACC
 }
-// mode 0: KKT factor in LDS; 1: register-resident QP (n+m <= 64); 2: KKT factor in HBM (large instances); 3: register-resident QP, 65..112 rows
 template <class Model> inline size_t sqp_eig_lds_bytes(int P, int S, const pmpc_sqp_settings* ss) {   // regularisation = 1: Jacobi workspace
     OcpDims<Model> dm(P, S);
     return ss->regularisation == 1 ? 2 * (size_t)dm.n * dm.n * sizeof(double) : 0;
 }
-template <class Model> inline size_t sqp_kernel_lds_bytes(int P, int S, int mode, int qp_solver = 0, bool pol = false, size_t cnd_staging = 0) {   // mode 6: condensed register QP on more than 64 variables, staging = cnd_staging (cond_qp_staging)
+// LDS layouts of sqp_kernel (dynamic bytes per instance: sqp_kernel_lds_bytes)
+enum class SqpLdsLayout {
+    LdsFactor,      // KKT factor in LDS (qp_solver = 1: the stacked (n + m)-row system)
+    HbmFactor,      // KKT factor in HBM (large instances): x, y, the right-hand side of the substitutions and the factorisation's diagonal tile; everything else in HBM
+    Reg1,           // register-resident QP, one KKT row per lane (n + m <= 64)
+    Reg2,           // register-resident QP, two KKT rows per lane, 65..112 rows
+    Reg2LdsTiles,   // the same, 113..128 rows: LDS-resident operand tiles
+    Cond1,          // condensed register QP on at most 64 variables (65..128 KKT rows)
+    Cond2,          // condensed register QP on more than 64 variables: staging = cnd_staging (cond_qp_staging)
+};
+template <class Model> inline size_t sqp_kernel_lds_bytes(int P, int S, SqpLdsLayout layout, int qp_solver = 0, bool pol = false, size_t cnd_staging = 0) {
     OcpDims<Model> dm(P, S);
-    if (mode == 0 && qp_solver == 1)
-        return (QpLds::doubles(dm.n, dm.m + dm.n) + SqpLds::doubles(dm.n, dm.m, dm.mi) + OcpLds<Model>::doubles(P, S) + 8 + FILTER_LDS_DOUBLES) * sizeof(double);
-    size_t stage = OcpLds<Model>::doubles(P, S);
-    if (mode == 1) { const size_t need = (size_t)RegKkt<64>::TRI + OcpLds<Model>::const_doubles(P, S) + 8; if (stage < need) stage = need; }
-    if (mode == 2)   // large instances: x, y, the right-hand side of the substitutions and the factorisation's diagonal tile; everything else in HBM
+    const size_t sqp = SqpLds::doubles(dm.n, dm.m, dm.mi), stage = OcpLds<Model>::doubles(P, S), cst = OcpLds<Model>::const_doubles(P, S);
+    const size_t filt = pol ? FILTER_LDS_DOUBLES : 0, jv = jview_doubles<Model>(dm.NN);
+    auto reg = [&](size_t qp_staging, size_t jview) {   // register-resident QP: x / y in LDS, the per-node staging at least the QP's staging, the block-sparse copy of J
+        const size_t need = qp_staging + cst + 8;
+        return (QpLds::doubles_xy(dm.n, dm.m) + sqp + (stage < need ? need : stage) + 8 + jview + filt) * sizeof(double);
+    };
+    switch (layout) {
+    case SqpLdsLayout::LdsFactor: return (QpLds::doubles(dm.n, qp_solver == 1 ? dm.m + dm.n : dm.m) + sqp + stage + 8 + FILTER_LDS_DOUBLES) * sizeof(double);
+    case SqpLdsLayout::HbmFactor:
         return (QpLds::doubles_xy(dm.n, dm.m) + (size_t)(dm.n + dm.m) + BigKkt::LDS_DOUBLES + BIG_MAIL_DOUBLES + (size_t)(P + 1) * (P + 2) + ((Model::NG == 0 && Model::NP == 0 && JViewRT<Model>::tab_worth_it(dm.NN)) ? JViewRT<Model>::tab_doubles(dm.NN) + 1 : 0) + (Model::ND > 0 ? Model::ND : 1) + FILTER_LDS_DOUBLES + 8) * sizeof(double);
-    if (mode == 3) { const size_t need = (size_t)RegKkt2<112>::TRI + OcpLds<Model>::const_doubles(P, S) + 8; if (stage < need) stage = need; }
-    if (mode == 5) { const size_t need = (size_t)RegKkt<64>::TRI + OcpLds<Model>::const_doubles(P, S) + 8; if (stage < need) stage = need; }   // condensed register QP on at most 64 variables (65..128 KKT rows)
-    if (mode == 4) { const size_t need = (size_t)RegKkt2<128>::TRI + OcpLds<Model>::const_doubles(P, S) + 8; if (stage < need) stage = need; }   // 113..128 rows: LDS-resident operand tiles
-    if (mode == 6) { const size_t need = cnd_staging + OcpLds<Model>::const_doubles(P, S) + 8; if (stage < need) stage = need; }
-    return ((mode == 0 ? QpLds::doubles(dm.n, dm.m) : QpLds::doubles_xy(dm.n, dm.m)) + SqpLds::doubles(dm.n, dm.m, dm.mi) + stage + 8 +
-            ((mode == 1 || mode == 3 || mode == 4 || mode == 5 || mode == 6) ? (mode == 1 ? 0 : jview_doubles<Model>(dm.NN)) + (pol ? FILTER_LDS_DOUBLES : 0) : FILTER_LDS_DOUBLES) + (mode == 2 ? BigKkt::LDS_DOUBLES : 0)) * sizeof(double);
+    case SqpLdsLayout::Reg1: return reg(RegKkt<64>::TRI, 0);
+    case SqpLdsLayout::Reg2: return reg(RegKkt2<112>::TRI, jv);
+    case SqpLdsLayout::Reg2LdsTiles: return reg(RegKkt2<128>::TRI, jv);
+    case SqpLdsLayout::Cond1: return reg(RegKkt<64>::TRI, jv);
+    case SqpLdsLayout::Cond2: return reg(cnd_staging, jv);
+    }
+    return 0;
 }
 constexpr int BIG_WG4_MAX_BATCH = 256;   // instances (on a 256-CU device) up to which the four-wavefront team kernel serves a large-instance batch (see sqp_launch_dev; measured: one workgroup per CU — 256: 11.9 -> 9.9 ms, 512: 13.5 -> 19.2)
 constexpr int BIG_TWO_WAVES_MAX_ROWS = 200;   // below: two wavefronts per SIMD on the HBM-factor kernel when the batch exceeds the SIMD count (see sqp_launch_dev)
@@ -633,181 +659,176 @@ template <> struct LDS_PATH_PROFILED<RobotOCP> { static constexpr bool value = t
 template <> struct LDS_PATH_PROFILED<CstrOCP> { static constexpr bool value = true; };
 template <> struct LDS_PATH_PROFILED<KiteStandInOCP> { static constexpr bool value = true; };
 
-// Launch the fused SQP kernel for `Model` on DEVICE buffers (asynchronous on the context's stream).
 #ifndef PMPC_EXPERIMENT_COND_SMALL
 #define PMPC_EXPERIMENT_COND_SMALL 0
 #endif
-#ifndef PMPC_EXPERIMENT_SMALL_POL
-#define PMPC_EXPERIMENT_SMALL_POL 0   /* 2: developer switch — the hook build of the small condensed kernel also under the DEFAULT policies (the bisection of EXPERIMENTS.md round 5, with -DPMPC_EXPERIMENT_CND_WITH_RUIZ) */
-#endif
-// Redo launch behind a one-row-per-lane register kernel (PMPC_FLAG_ILLCOND, include/polympc_amd.h): the instances whose constraint-first QP gave up at
-// its conditioning gate (none on any BASELINE workload) are solved again, from their guesses, by the LDS-resident kernel — static LDL^T of the
-// (n + m)-row KKT matrix with substitutions; every other workgroup reads one word and exits. PMPC_NO_REDO_LAUNCH=1: developer switch (timing the launch).
+// Launch plan of the fused SQP kernel: the route a selection function (plan_reg, sqp_launch_dev) decided on, launched by launch_sqp_plan
+template <class Model> using SqpKernel = decltype(&sqp_kernel<Model>);   // (every instantiation of sqp_kernel / sqp_kernel_rr shares one function type)
+template <class Model> struct SqpPlan {
+    int route = PMPC_ROUTE_NONE;   // recorded for pmpc_sqp_last_route
+    SqpKernel<Model> kern = nullptr;
+    size_t lds = 0;                // dynamic LDS bytes
+    unsigned threads = WAVE;       // 4 * WAVE: the four-wavefront team kernel
+    bool timed = false;            // the phase timers are passed
+    double* Kws = nullptr;         // HBM factor workspace (large-instance kernels)
+    decltype(&sqp_kernel_rr<Model, 1, 0, 0>) rr = nullptr;   // round-robin execution (PMPC_SQP_RR=1) in place of the iteration-sliced launches
+    decltype(&sqp_rr_init_kernel<Model>) rr_init = nullptr;
+    SqpKernel<Model> redo = nullptr;   // redo launch behind a kernel with a conditioning gate: the instances that gave up, solved again from their guesses
+    size_t redo_lds = 0;
+    bool redo_full_form = false;   // the redo runs with kkt_form = 1
+};
+
 template <class Model>
-inline bool launch_redo_generic(pmpc_context* ctx, const Model& mdl, const ChebData* cd, int P, int S, int B, const double* x_guess, const double* lam_guess, const double* d,
-                                const double* lbx, const double* ubx, const double* lbg, const double* ubg, const pmpc_sqp_settings* ss,
-                                const pmpc_qp_settings* qs, double* Hws, double* Aws, double* x, double* lam, pmpc_sqp_info* info, hipStream_t stream,
-                                size_t lds_limit) {
-    if (pmpc_internal_switch(ctx, PMPC_SW_NO_REDO_LAUNCH)) return true;
-    const size_t ldsg = sqp_kernel_lds_bytes<Model>(P, S, 0, 0) + sqp_eig_lds_bytes<Model>(P, S, ss);
-    if (ldsg > lds_limit) return true;   // (systems of at most 64 rows always fit)
-    auto gk = sqp_kernel<Model>;
-    if (hipFuncSetAttribute((const void*)gk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsg) != hipSuccess) return false;
-    pmpc_sqp_settings ssf = *ss; ssf.kkt_form = 1;
-    hipLaunchKernelGGL(gk, dim3(B), dim3(WAVE), ldsg, stream, mdl, cd, B, x_guess, lam_guess, d, lbx, ubx, lbg, ubg, ssf, *qs, Hws, Aws, x, lam, info,
-                       (unsigned long long*)nullptr, (double*)nullptr, PMPC_REDO_MODE, ss->max_iter, (double*)nullptr, (unsigned)(ldsg / sizeof(double)));
+inline void launch_sqp_kernel(SqpKernel<Model> kern, const SqpArgs<Model>& a, unsigned threads, size_t lds, const pmpc_sqp_settings& ss, unsigned long long* phase,
+                              double* Kws, int it_begin, int it_end, double* slice_state) {
+    hipLaunchKernelGGL(kern, dim3(a.B), dim3(threads), lds, a.stream, a.mdl, a.cd, a.B, a.x_guess, a.lam_guess, a.d, a.lbx, a.ubx, a.lbg, a.ubg, ss, *a.qs,
+                       a.Hws, a.Aws, a.x, a.lam, a.info, phase, Kws, it_begin, it_end, slice_state, (unsigned)(lds / sizeof(double)));
+}
+// the redo step of a plan (every other workgroup reads one word and exits); false: the LDS attribute could not be set
+template <class Model> inline bool launch_redo(const SqpPlan<Model>& p, const SqpArgs<Model>& a) {
+    if (!p.redo) return true;
+    if (!set_lds_attr(p.redo, p.redo_lds)) return false;
+    pmpc_sqp_settings ss = *a.ss;
+    if (p.redo_full_form) ss.kkt_form = 1;
+    launch_sqp_kernel(p.redo, a, WAVE, p.redo_lds, ss, nullptr, p.Kws, PMPC_REDO_MODE, a.ss->max_iter, nullptr);
     return true;
 }
+template <class Model> inline pmpc_status launch_sqp_plan(pmpc_context* ctx, const SqpPlan<Model>& p, const SqpArgs<Model>& a) {
+    const pmpc_sqp_settings& ss = *a.ss;
+    unsigned long long* phase = p.timed ? a.phase : nullptr;
+    pmpc_internal_set_route(ctx, p.route);
+    if (!set_lds_attr(p.kern, p.lds)) return PMPC_ERR_HIP;
+    if (p.rr) {   // one SQP iteration per work item, round-robin over the instances (sqp_kernel_rr), then the resume-mode launch for whatever is left in progress
+        if (!set_lds_attr(p.rr, p.lds)) return PMPC_ERR_HIP;
+        int* queue = (int*)(a.slice_state + (size_t)a.B * 2 * OcpDims<Model>(a.P, a.S).n);   // behind the slice state (sqp_launch_dev sizes the workspace for it)
+        const size_t words = (size_t)a.B * ss.max_iter > (size_t)RR_HEADER_WORDS ? (size_t)a.B * ss.max_iter : (size_t)RR_HEADER_WORDS;
+        hipLaunchKernelGGL(p.rr_init, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, a.stream, queue, a.info, a.B, ss.max_iter);
+        hipLaunchKernelGGL(p.rr, dim3(PMPC_SQP_WAVES * pmpc_internal_simd_count(ctx)), dim3(WAVE), p.lds, a.stream, a.mdl, a.cd, a.B, a.x_guess, a.lam_guess, a.d,
+                           a.lbx, a.ubx, a.lbg, a.ubg, ss, *a.qs, a.Hws, a.x, a.lam, a.info, a.slice_state, queue, (unsigned)(p.lds / sizeof(double)), phase);
+        launch_sqp_kernel(p.kern, a, p.threads, p.lds, ss, phase, p.Kws, -1, ss.max_iter, a.slice_state);
+    } else {
+        const int slice = (a.slice_state && a.slice_iters > 0) ? a.slice_iters : ss.max_iter;
+        for (int it = 0; it < ss.max_iter; it += slice) launch_sqp_kernel(p.kern, a, p.threads, p.lds, ss, phase, p.Kws, it, it + slice, a.slice_state);
+    }
+    if (!launch_redo(p, a)) return PMPC_ERR_HIP;
+    return launch_status();
+}
+
+// Redo step behind a one-row-per-lane register kernel or the block-structured kernel (PMPC_FLAG_ILLCOND, include/polympc_amd.h): the instances whose QP gave up
+// at its conditioning gate (none on any BASELINE workload) are solved again, from their guesses, by the LDS-resident kernel — static LDL^T of the (n + m)-row
+// KKT matrix with substitutions. PMPC_NO_REDO_LAUNCH=1: developer switch (timing the launch).
+template <class Model> inline void plan_redo_lds(pmpc_context* ctx, const SqpArgs<Model>& a, SqpPlan<Model>& p) {
+    if (pmpc_internal_switch(ctx, PMPC_SW_NO_REDO_LAUNCH)) return;
+    const size_t lds = sqp_kernel_lds_bytes<Model>(a.P, a.S, SqpLdsLayout::LdsFactor) + sqp_eig_lds_bytes<Model>(a.P, a.S, a.ss);
+    // ADVICE: no redo step when the LDS-resident kernel does not fit — the instances that gave up keep the internal REDO status (systems of at most 64 rows always fit)
+    if (lds > a.lds_limit) return;
+    p.redo = sqp_kernel<Model>; p.redo_lds = lds; p.redo_full_form = true;
+}
 template <class Model, int NN_, int MM_> struct COND_REG_OK { static constexpr bool value = NN_ + MM_ > WAVE && NN_ <= 112 && MM_ > 0 && MM_ <= WAVE && Model::NP <= 1; };   // (NP = 1 and NG > 0 since round 6: the parameter's dense column of A as a wave reduction, the path-constraint rows as own-node blocks without a D~ row)
-// Register-resident QP specialisations are selected from the compile-time model dimensions and the runtime node count
-// when the KKT system has at most 64 rows; otherwise the LDS-resident path is used.
+// Register-resident QP specialisations are selected from the compile-time model dimensions and the runtime node count: one KKT row per lane up to
+// 64 rows, two rows per lane up to 128 (the Hessian-update policy is a run-time choice there); false: this grid has no register kernel for the request.
 template <class Model, int NNODES, bool LEAN = false>   // LEAN: no phase-timer and no block-BFGS specialisation (pmpc_grids.hpp: those requests take the LDS-resident kernel)
-inline bool try_launch_reg(pmpc_context* ctx, const Model& mdl, const ChebData* cd, int P, int S, int B, const double* x_guess,
-                           const double* lam_guess, const double* d, const double* lbx, const double* ubx, const double* lbg,
-                           const double* ubg, const pmpc_sqp_settings* ss, const pmpc_qp_settings* qs, double* Hws, double* Aws, double* x,
-                           double* lam, pmpc_sqp_info* info, hipStream_t stream, size_t lds_limit, unsigned long long* phase, pmpc_status* st,
-                           double* slice_state, int slice_iters) {
+inline bool plan_reg(pmpc_context* ctx, const SqpArgs<Model>& a, SqpPlan<Model>& p) {
     constexpr int NN_ = (Model::NX + Model::NU) * NNODES + Model::NP;
     constexpr int MM_ = (Model::NX + Model::NG) * NNODES;
+    constexpr bool ONE_ROW = NN_ + MM_ <= WAVE;
+    const pmpc_sqp_settings* ss = a.ss;
     // the policy hooks the reference's tests install beside the defaults — Ruiz preconditioner, filter line search — exist on the register paths
     // for the grids of its own tests (7, 11 and — where the model fits 128 rows — 16 nodes) as separate kernels (POL); any other grid takes the LDS /
     // HBM-resident kernels for them
     const bool pol = ss->preconditioner == 1 || ss->line_search == 1 || ss->regularisation == 1;   // (regularisation = 1, eigenvalue mirroring — sqp_test_autodiff.cpp:29-45: Jacobi workspace of 16 n^2 bytes of LDS, round 6)
     constexpr bool POLK = ((!LEAN && (NNODES == 7 || NNODES == 11)) || NNODES == 16) && (int)OcpDims<Model>::NDER <= RUIZ_MAX_NDER;   // (16 nodes: the reference's mpc_wrapper_test grid, round 4)
-    if (pol && !POLK) return false;
-    if constexpr (NN_ + MM_ <= WAVE) {
-        if (P * S + 1 != NNODES) return false;
-        const size_t ldsr = sqp_kernel_lds_bytes<Model>(P, S, 1, 0, pol) + sqp_eig_lds_bytes<Model>(P, S, ss);
-        if (ldsr > lds_limit) return false;
-        if (LEAN && (ss->hessian_update == 1 || phase)) return false;
-        pmpc_internal_set_route(ctx, PMPC_ROUTE_REG1);
-        auto kern = sqp_kernel<Model, NN_, MM_, false>;
-        if constexpr (!LEAN)
-            kern = (ss->hessian_update == 1) ? sqp_kernel<Model, NN_, MM_, false, 1>   // (no phase timers in the block-BFGS specialisation)
-                                             : (phase ? sqp_kernel<Model, NN_, MM_, true> : sqp_kernel<Model, NN_, MM_, false>);
-        if constexpr (POLK) { if (pol) kern = (ss->hessian_update == 1) ? sqp_kernel<Model, NN_, MM_, false, 1, false, false, true> : sqp_kernel<Model, NN_, MM_, false, 0, false, false, true>; }
-#if PMPC_EXPERIMENT_COND_SMALL   /* developer experiment (round 6, EXPERIMENTS.md): the CONDENSED register QP (pmpc_qp_cond.hpp) on a grid of at most 64 KKT rows — config A on 35 instead of 56 rows */
-        size_t ldsc = ldsr;
-        if constexpr (!LEAN && NNODES == 7 && Model::NP == 0 && Model::NG == 0) {
-            if (!pol && ss->kkt_form == 0 && ss->hessian_update == 0 && !phase && !pmpc_internal_switch(ctx, PMPC_SW_NO_CONDREG)) {
-                kern = sqp_kernel<Model, NN_, MM_, false, 0, false, false, false, true>;
-                ldsc = sqp_kernel_lds_bytes<Model>(P, S, 5, 0, false);
-                pmpc_internal_set_route(ctx, PMPC_ROUTE_CONDREG);
-            }
-        }
-        if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsc) != hipSuccess) { *st = PMPC_ERR_HIP; return true; }
-        if (pmpc_internal_last_route(ctx) == PMPC_ROUTE_CONDREG) {
-            hipLaunchKernelGGL(kern, dim3(B), dim3(WAVE), ldsc, stream, mdl, cd, B, x_guess, lam_guess, d, lbx, ubx, lbg, ubg,
-                               *ss, *qs, Hws, Aws, x, lam, info, phase, (double*)nullptr, 0, ss->max_iter, (double*)nullptr, (unsigned)(ldsc / sizeof(double)));
-            if (!launch_redo_generic<Model>(ctx, mdl, cd, P, S, B, x_guess, lam_guess, d, lbx, ubx, lbg, ubg, ss, qs, Hws, Aws, x, lam, info, stream, lds_limit)) { *st = PMPC_ERR_HIP; return true; }
-            *st = (hipGetLastError() == hipSuccess) ? PMPC_OK : PMPC_ERR_HIP;
-            return true;
-        }
-#endif
-        if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsr) != hipSuccess) { *st = PMPC_ERR_HIP; return true; }
-        const int slice = (slice_state && slice_iters > 0) ? slice_iters : ss->max_iter;
-        if constexpr (!LEAN) {
-            // more instances than resident wavefronts: one SQP iteration per work item, round-robin over the instances (sqp_kernel_rr)
-            const int slots = PMPC_SQP_WAVES * pmpc_internal_simd_count(ctx);
-            #ifdef PMPC_RR_PROFILE
-            const bool rr_phase_ok = true;
+    if constexpr (NN_ + MM_ > 128) return false;
+    else {
+        // size checks
+        if ((pol && !POLK) || a.P * a.S + 1 != NNODES) return false;
+        constexpr SqpLdsLayout layout = ONE_ROW ? SqpLdsLayout::Reg1 : (NN_ + MM_ <= 112 ? SqpLdsLayout::Reg2 : SqpLdsLayout::Reg2LdsTiles);
+        const size_t lds_full = sqp_kernel_lds_bytes<Model>(a.P, a.S, layout, 0, pol) + sqp_eig_lds_bytes<Model>(a.P, a.S, ss);
+        if (lds_full > a.lds_limit) return false;
+        if (ONE_ROW && LEAN && (ss->hessian_update == 1 || a.phase)) return false;
+        // the full-inverse kernel
+        p.route = ONE_ROW ? PMPC_ROUTE_REG1 : PMPC_ROUTE_REG2;
+        p.kern = sqp_kernel<Model, NN_, MM_, false>;
+        p.lds = lds_full;
+        if constexpr (ONE_ROW) {
+            p.timed = true;
+            if constexpr (!LEAN)
+                p.kern = (ss->hessian_update == 1) ? sqp_kernel<Model, NN_, MM_, false, 1>   // (no phase timers in the block-BFGS specialisation)
+                                                   : (a.phase ? sqp_kernel<Model, NN_, MM_, true> : sqp_kernel<Model, NN_, MM_, false>);
+            plan_redo_lds(ctx, a, p);
+            if constexpr (!LEAN) {   // more instances than resident wavefronts: one SQP iteration per work item (PMPC_SQP_RR=1, sqp_kernel_rr)
+#ifdef PMPC_RR_PROFILE
+                const bool rr_phase_ok = true;
 #else
-            const bool rr_phase_ok = !phase;
+                const bool rr_phase_ok = !a.phase;
 #endif
-            if (!pol && slice_state && slice_iters == 0 && rr_phase_ok && ss->max_iter > 1 && ss->max_iter <= RR_MAX_ITER && B > slots && B <= RR_MAX_BATCH && (size_t)B * ss->max_iter < ((size_t)1 << 30) && pmpc_internal_sqp_rr(ctx)) {
-                auto rrk = (ss->hessian_update == 1) ? sqp_kernel_rr<Model, NN_, MM_, 1> : sqp_kernel_rr<Model, NN_, MM_, 0>;
-                if (hipFuncSetAttribute((const void*)rrk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsr) != hipSuccess) { *st = PMPC_ERR_HIP; return true; }
-                int* queue = (int*)(slice_state + (size_t)B * 2 * NN_);   // behind the slice state (sqp_launch_dev sizes the workspace for it)
-                { const size_t words = (size_t)B * ss->max_iter > (size_t)RR_HEADER_WORDS ? (size_t)B * ss->max_iter : (size_t)RR_HEADER_WORDS;
-                  hipLaunchKernelGGL(sqp_rr_init_kernel<Model>, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, stream, queue, info, B, ss->max_iter); }
-                hipLaunchKernelGGL(rrk, dim3(slots), dim3(WAVE), ldsr, stream, mdl, cd, B, x_guess, lam_guess, d, lbx, ubx, lbg, ubg,
-                                   *ss, *qs, Hws, x, lam, info, slice_state, queue, (unsigned)(ldsr / sizeof(double)), phase);
-                // resume mode: a no-op per instance unless something was left in progress (see sqp_kernel_rr)
-                hipLaunchKernelGGL(kern, dim3(B), dim3(WAVE), ldsr, stream, mdl, cd, B, x_guess, lam_guess, d, lbx, ubx, lbg, ubg,
-                                   *ss, *qs, Hws, Aws, x, lam, info, phase, (double*)nullptr, -1, ss->max_iter, slice_state, (unsigned)(ldsr / sizeof(double)));
-                if (!launch_redo_generic<Model>(ctx, mdl, cd, P, S, B, x_guess, lam_guess, d, lbx, ubx, lbg, ubg, ss, qs, Hws, Aws, x, lam, info, stream, lds_limit)) { *st = PMPC_ERR_HIP; return true; }
-                *st = (hipGetLastError() == hipSuccess) ? PMPC_OK : PMPC_ERR_HIP;
-                return true;
+                const int slots = PMPC_SQP_WAVES * pmpc_internal_simd_count(ctx);
+                if (!pol && a.slice_state && a.slice_iters == 0 && rr_phase_ok && ss->max_iter > 1 && ss->max_iter <= RR_MAX_ITER && a.B > slots && a.B <= RR_MAX_BATCH &&
+                    (size_t)a.B * ss->max_iter < ((size_t)1 << 30) && pmpc_internal_sqp_rr(ctx)) {
+                    p.rr = (ss->hessian_update == 1) ? sqp_kernel_rr<Model, NN_, MM_, 1> : sqp_kernel_rr<Model, NN_, MM_, 0>;
+                    p.rr_init = sqp_rr_init_kernel<Model>;
+                }
+            }
+        } else if constexpr (LDS_PATH_PROFILED<Model>::value && !LEAN) {   // developer builds with phase timers
+            if (a.phase && !pol) { p.kern = sqp_kernel<Model, NN_, MM_, true>; p.timed = true; }
+        }
+        // condensed override (pmpc_qp_cond.hpp): the condensed register QP; kkt_form = 1 keeps the full inverse, which serves the redo launch behind it
+        const bool condreg = ss->kkt_form == 0 && !pmpc_internal_switch(ctx, PMPC_SW_NO_CONDREG);
+        auto condensed = [&](SqpKernel<Model> kern, size_t lds, bool timed, SqpKernel<Model> full) {
+            p.route = PMPC_ROUTE_CONDREG; p.kern = kern; p.lds = lds; p.timed = timed;
+            if (!pmpc_internal_switch(ctx, PMPC_SW_NO_REDO_LAUNCH)) { p.redo = full; p.redo_lds = lds_full; }
+        };
+#if PMPC_EXPERIMENT_COND_SMALL   /* developer experiment (round 6, EXPERIMENTS.md): the CONDENSED register QP on a grid of at most 64 KKT rows — config A on 35 instead of 56 rows; the redo stays on the LDS-resident kernel */
+        if constexpr (ONE_ROW && !LEAN && NNODES == 7 && Model::NP == 0 && Model::NG == 0) {
+            if (!pol && condreg && ss->hessian_update == 0 && !a.phase) {
+                p.route = PMPC_ROUTE_CONDREG; p.kern = sqp_kernel<Model, NN_, MM_, false, 0, false, false, false, true>; p.rr = nullptr;
+                p.lds = sqp_kernel_lds_bytes<Model>(a.P, a.S, SqpLdsLayout::Cond1);
             }
         }
-        for (int it = 0; it < ss->max_iter; it += slice)
-            hipLaunchKernelGGL(kern, dim3(B), dim3(WAVE), ldsr, stream, mdl, cd, B, x_guess, lam_guess, d, lbx, ubx, lbg, ubg,
-                               *ss, *qs, Hws, Aws, x, lam, info, phase, (double*)nullptr, it, it + slice, slice_state, (unsigned)(ldsr / sizeof(double)));
-        if (!launch_redo_generic<Model>(ctx, mdl, cd, P, S, B, x_guess, lam_guess, d, lbx, ubx, lbg, ubg, ss, qs, Hws, Aws, x, lam, info, stream, lds_limit)) { *st = PMPC_ERR_HIP; return true; }
-        *st = (hipGetLastError() == hipSuccess) ? PMPC_OK : PMPC_ERR_HIP;
-        return true;
-    } else if constexpr (NN_ + MM_ <= 128) {   // two KKT rows per lane (pmpc_qp_reg2.hpp); the Hessian-update policy is a run-time choice there
-        if (P * S + 1 != NNODES) return false;
-        const size_t ldsr = sqp_kernel_lds_bytes<Model>(P, S, NN_ + MM_ <= 112 ? 3 : 4, 0, pol) + sqp_eig_lds_bytes<Model>(P, S, ss);
-        if (ldsr > lds_limit) return false;
-        pmpc_internal_set_route(ctx, PMPC_ROUTE_REG2);
-        auto kern = sqp_kernel<Model, NN_, MM_, false>;
-        bool timed = false;
-        if constexpr (LDS_PATH_PROFILED<Model>::value && !LEAN) { if (phase && !pol) { kern = sqp_kernel<Model, NN_, MM_, true>; timed = true; } }   // developer builds with phase timers
-        if constexpr (POLK) { if (pol) kern = sqp_kernel<Model, NN_, MM_, false, 0, false, false, true>; }
-        // condensed register QP (pmpc_qp_cond.hpp): 65..112 variables, at most 64 constraint rows, the default policies; kkt_form = 1 keeps the full inverse
-        size_t ldsq = ldsr;
-        if constexpr (COND_REG_OK<Model, NN_, MM_>::value) {
-            if (!pol && ss->kkt_form == 0 && !pmpc_internal_switch(ctx, PMPC_SW_NO_CONDREG)) {
-                if constexpr (NN_ <= WAVE) ldsq = sqp_kernel_lds_bytes<Model>(P, S, 5, 0, false);   // (two wavefronts per SIMD: a smaller staging lets more instances share a CU)
-                else ldsq = sqp_kernel_lds_bytes<Model>(P, S, 6, 0, false, (size_t)cond_qp_staging<NN_, MM_, NNODES>());   // (its own tile set's staging, not the full inverse's: four instead of three instances per CU on the 16-node grid)
-                kern = sqp_kernel<Model, NN_, MM_, false, 0, false, false, false, true>; timed = false;
-                if constexpr (LDS_PATH_PROFILED<Model>::value && !LEAN) { if (phase) { kern = sqp_kernel<Model, NN_, MM_, true, 0, false, false, false, true>; timed = true; } }
-                pmpc_internal_set_route(ctx, PMPC_ROUTE_CONDREG);
-#if PMPC_EXPERIMENT_SMALL_POL == 2   /* developer experiment: the hook variant of the small condensed kernel under the DEFAULT policies */
-                if constexpr (POLK && NN_ <= WAVE) { kern = sqp_kernel<Model, NN_, MM_, false, 0, false, false, true, true>; ldsq = sqp_kernel_lds_bytes<Model>(P, S, 3, 0, true); }
 #endif
+        if constexpr (COND_REG_OK<Model, NN_, MM_>::value) {   // 65..112 variables, at most 64 constraint rows, the default policies
+            if (!pol && condreg) {
+                size_t lds;
+                if constexpr (NN_ <= WAVE) lds = sqp_kernel_lds_bytes<Model>(a.P, a.S, SqpLdsLayout::Cond1);   // (two wavefronts per SIMD: a smaller staging lets more instances share a CU)
+                else lds = sqp_kernel_lds_bytes<Model>(a.P, a.S, SqpLdsLayout::Cond2, 0, false, (size_t)cond_qp_staging<NN_, MM_, NNODES>());   // (its own tile set's staging, not the full inverse's: four instead of three instances per CU on the 16-node grid)
+                bool timed = false;
+                auto kern = sqp_kernel<Model, NN_, MM_, false, 0, false, false, false, true>;
+                if constexpr (LDS_PATH_PROFILED<Model>::value && !LEAN) { if (a.phase) { kern = sqp_kernel<Model, NN_, MM_, true, 0, false, false, false, true>; timed = true; } }
+                condensed(kern, lds, timed, sqp_kernel<Model, NN_, MM_, false>);
             }
-            // the hooks keep the condensed QP — the filter line search and eigenvalue mirroring since rounds 4 / 6, the Ruiz preconditioner since late round 6: it rescales the
-            // workspace, so the hook builds read their D~ tables (one set per state index) and, after an equilibration, the node blocks back from it (pmpc_qp_cond.hpp WS)
-            if constexpr (POLK) {
-                if (pol && ss->kkt_form == 0 && !pmpc_internal_switch(ctx, PMPC_SW_NO_CONDREG) && !(ss->preconditioner == 1 && pmpc_internal_switch(ctx, PMPC_SW_NO_CONDREG_RUIZ))) {
-                    const size_t stg = ss->preconditioner == 1 ? (size_t)cond_qp_staging_ws<NN_, MM_, NNODES, Model::NX>() : (size_t)cond_qp_staging<NN_, MM_, NNODES>();   // (the tables per state index only with the Ruiz preconditioner: the other hooks keep the smaller staging — more instances per CU)
-                    const size_t ldsw = sqp_kernel_lds_bytes<Model>(P, S, 6, 0, true, stg) + sqp_eig_lds_bytes<Model>(P, S, ss);
-                    if (ldsw <= lds_limit) {
-                        kern = sqp_kernel<Model, NN_, MM_, false, 0, false, false, true, true>; timed = false;
-                        ldsq = ldsw;
-                        pmpc_internal_set_route(ctx, PMPC_ROUTE_CONDREG);
+        }
+        // hook override: the builds with the policy hooks compiled in (POL)
+        if constexpr (POLK) {
+            if (pol) {
+                p.kern = sqp_kernel<Model, NN_, MM_, false, 0, false, false, true>;
+                if constexpr (ONE_ROW) { if (ss->hessian_update == 1) p.kern = sqp_kernel<Model, NN_, MM_, false, 1, false, false, true>; }
+                const SqpKernel<Model> full = p.kern;
+                // the hooks keep the condensed QP — the filter line search and eigenvalue mirroring since rounds 4 / 6, the Ruiz preconditioner since late round 6: it rescales the
+                // workspace, so the hook builds read their D~ tables (one set per state index) and, after an equilibration, the node blocks back from it (pmpc_qp_cond.hpp WS)
+                if constexpr (COND_REG_OK<Model, NN_, MM_>::value) {
+                    if (condreg && !(ss->preconditioner == 1 && pmpc_internal_switch(ctx, PMPC_SW_NO_CONDREG_RUIZ))) {
+                        const size_t stg = ss->preconditioner == 1 ? (size_t)cond_qp_staging_ws<NN_, MM_, NNODES, Model::NX>() : (size_t)cond_qp_staging<NN_, MM_, NNODES>();   // (the tables per state index only with the Ruiz preconditioner: the other hooks keep the smaller staging — more instances per CU)
+                        const size_t lds = sqp_kernel_lds_bytes<Model>(a.P, a.S, SqpLdsLayout::Cond2, 0, true, stg) + sqp_eig_lds_bytes<Model>(a.P, a.S, ss);
+                        if (lds <= a.lds_limit) condensed(sqp_kernel<Model, NN_, MM_, false, 0, false, false, true, true>, lds, false, full);
                     }
                 }
             }
         }
-        auto kern_full = sqp_kernel<Model, NN_, MM_, false>;   // the full two-rows-per-lane inverse: serves the redo launch behind a condensed kernel
-        if constexpr (POLK) { if (pol) kern_full = sqp_kernel<Model, NN_, MM_, false, 0, false, false, true>; }
-        if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsq) != hipSuccess) { *st = PMPC_ERR_HIP; return true; }
-        const int slice = (slice_state && slice_iters > 0) ? slice_iters : ss->max_iter;
-        for (int it = 0; it < ss->max_iter; it += slice)
-            hipLaunchKernelGGL(kern, dim3(B), dim3(WAVE), ldsq, stream, mdl, cd, B, x_guess, lam_guess, d, lbx, ubx, lbg, ubg,
-                               *ss, *qs, Hws, Aws, x, lam, info, timed ? phase : (unsigned long long*)nullptr, (double*)nullptr, it, it + slice, slice_state, (unsigned)(ldsq / sizeof(double)));
-        if (pmpc_internal_last_route(ctx) == PMPC_ROUTE_CONDREG && !pmpc_internal_switch(ctx, PMPC_SW_NO_REDO_LAUNCH)) {
-            // redo launch: the instances whose condensed solve gave up at its conditioning gate (PMPC_FLAG_ILLCOND; none on any BASELINE workload) are solved
-            // again, from their guesses, by the full-inverse kernel of this size — every other workgroup reads one word and exits
-            if (hipFuncSetAttribute((const void*)kern_full, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsr) != hipSuccess) { *st = PMPC_ERR_HIP; return true; }
-            hipLaunchKernelGGL(kern_full, dim3(B), dim3(WAVE), ldsr, stream, mdl, cd, B, x_guess, lam_guess, d, lbx, ubx, lbg, ubg,
-                               *ss, *qs, Hws, Aws, x, lam, info, (unsigned long long*)nullptr, (double*)nullptr, PMPC_REDO_MODE, ss->max_iter, (double*)nullptr, (unsigned)(ldsr / sizeof(double)));
-        }
-        *st = (hipGetLastError() == hipSuccess) ? PMPC_OK : PMPC_ERR_HIP;
         return true;
-    } else {
-        return false;
     }
 }
 
 // Register-resident specialisations for further node counts live in their own translation units (pmpc_grids_*.hip, built-in models only: a user OCP's
-// translation unit instantiates the three grids below and takes the LDS / HBM-factor kernels elsewhere). Same arguments and meaning as try_launch_reg.
+// translation unit instantiates the three grids below and takes the LDS / HBM-factor kernels elsewhere). Same arguments and meaning as plan_reg.
 template <class Model> struct EXTRA_GRIDS { static constexpr bool value = false; };
 template <> struct EXTRA_GRIDS<RobotOCP> { static constexpr bool value = true; };      // (declared here for every translation unit, see LDS_PATH_PROFILED)
 template <> struct EXTRA_GRIDS<CstrOCP> { static constexpr bool value = true; };
 template <> struct EXTRA_GRIDS<ParkingOCP> { static constexpr bool value = true; };
 template <> struct EXTRA_GRIDS<RobotNGOCP> { static constexpr bool value = true; };
 template <> struct EXTRA_GRIDS<ParkingNGOCP> { static constexpr bool value = true; };
-template <class Model>
-bool try_launch_extra_grids(pmpc_context* ctx, const Model& mdl, const ChebData* cd, int P, int S, int B, const double* x_guess,
-                            const double* lam_guess, const double* d, const double* lbx, const double* ubx, const double* lbg,
-                            const double* ubg, const pmpc_sqp_settings* ss, const pmpc_qp_settings* qs, double* Hws, double* Aws, double* x,
-                            double* lam, pmpc_sqp_info* info, hipStream_t stream, size_t lds_limit, unsigned long long* phase, pmpc_status* st,
-                            double* slice_state, int slice_iters);
+template <class Model> bool plan_extra_grids(pmpc_context* ctx, const SqpArgs<Model>& a, SqpPlan<Model>& p);
 
+// Launch the fused SQP kernel for `Model` on DEVICE buffers (asynchronous on the context's stream): block-structured kernel → register grids → LDS / HBM-factor / team kernel.
 template <class Model>
 inline pmpc_status sqp_launch_dev(pmpc_context* ctx, const Model& mdl, int P, int S, double t0, double tf, int B, const double* x_guess,
                                   const double* lam_guess, const double* d, const double* lbx, const double* ubx, const double* lbg,
@@ -824,107 +845,100 @@ inline pmpc_status sqp_launch_dev(pmpc_context* ctx, const Model& mdl, int P, in
                              (size_t)B * ss->max_iter < ((size_t)1 << 30);
     pmpc_status st = pmpc_internal_services(ctx, P, S, t0, tf, base * sizeof(double) + (rr_possible ? rr_queue_bytes(B, ss->max_iter) : 0), &cdv, &ws, &streamv, &lds_limit, &phase, &force_lds);
     if (st != PMPC_OK) return st;
-    const ChebData* cd = (const ChebData*)cdv;
-    hipStream_t stream = (hipStream_t)streamv;
-    double* Hws = ws; double* Aws = ws + (size_t)B * dm.n * dm.n;
-    double* slice_state = Aws + (size_t)B * dm.m * dm.n;
     const int slice_iters = ss->line_search == 1 ? 0 : pmpc_internal_sqp_slice(ctx);   // (the filter lives in LDS for the whole solve)
     if ((ss->hessian_update != 0 && ss->hessian_update != 1) || (ss->qp_solver != 0 && ss->qp_solver != 1)) return PMPC_ERR_INVALID_ARGUMENT;
     if ((ss->line_search != 0 && ss->line_search != 1) ||
         (ss->line_search == 1 && (ss->filter_max_depth < 1 || ss->filter_max_depth > PMPC_FILTER_MAX_DEPTH))) return PMPC_ERR_INVALID_ARGUMENT;
     if (qs->linear_solver != 0 && qs->linear_solver != 1) return PMPC_ERR_INVALID_ARGUMENT;
+    SqpArgs<Model> a{mdl, (const ChebData*)cdv, P, S, B, x_guess, lam_guess, d, lbx, ubx, lbg, ubg, x, lam, info, ss, qs,
+                     ws, ws + (size_t)B * dm.n * dm.n, (hipStream_t)streamv, lds_limit, phase, ws + (size_t)B * dm.n * dm.n + (size_t)B * dm.m * dm.n, slice_iters};
     if constexpr (SCHUR_GRIDS<Model>::value) {   // block-diagonal Hessian on a grid with a block-structured kernel
         // (the redo launch behind this kernel's conditioning gate runs the LDS-resident kernel: a grid it does not fit — only under a developer's PMPC_LDS_LIMIT —
         //  keeps the dense kernels, so that an instance that gave up can always be solved again)
-        if (!force_lds && !pmpc_internal_switch(ctx, PMPC_SW_NO_SCHUR) && schur_request_ok(ss, qs, slice_iters) && sqp_kernel_lds_bytes<Model>(P, S, 0, 0) <= lds_limit) {
+        if (!force_lds && !pmpc_internal_switch(ctx, PMPC_SW_NO_SCHUR) && schur_request_ok(ss, qs, slice_iters) && sqp_kernel_lds_bytes<Model>(P, S, SqpLdsLayout::LdsFactor) <= lds_limit) {
             pmpc_status rst = PMPC_OK;
-            if (try_launch_schur_grids<Model>(ctx, mdl, cd, P, S, B, x_guess, lam_guess, d, lbx, ubx, ss, qs, x, lam, info, stream, lds_limit, phase, &rst)) {
+            if (try_launch_schur_grids<Model>(ctx, a, &rst)) {
                 // redo launch: the instances whose block-structured QP gave up at its conditioning gate (PMPC_SCHUR_COND_GATE; none on any BASELINE workload) are
                 // solved again, from their guesses, on the LDS-resident static LDL^T of the (n + m)-row matrix (every compiled grid fits)
-                if (rst == PMPC_OK && !launch_redo_generic<Model>(ctx, mdl, cd, P, S, B, x_guess, lam_guess, d, lbx, ubx, lbg, ubg, ss, qs, Hws, Aws, x, lam, info, stream, lds_limit)) rst = PMPC_ERR_HIP;
+                SqpPlan<Model> redo;
+                if (rst == PMPC_OK) plan_redo_lds(ctx, a, redo);
+                if (rst == PMPC_OK && !launch_redo(redo, a)) rst = PMPC_ERR_HIP;
                 return rst;
             }
         }
     }
     // kkt_form = 2 asks for the block-structured range-space form where a specialisation is compiled (above); everywhere else it means the default
     pmpc_sqp_settings ss_default_form;
-    if (ss->kkt_form == 2) { ss_default_form = *ss; ss_default_form.kkt_form = 0; ss = &ss_default_form; }
-    if (!force_lds && ss->qp_solver == 0 && qs->linear_solver == 0) {   // (preconditioner / line_search = 1: the 7- and 11-node register kernels carry them, see try_launch_reg)   // node counts whose KKT system can fit 64 rows for small models (7 nodes: config A / D); Ruiz: LDS path
-        pmpc_status rst = PMPC_OK;
-        if (try_launch_reg<Model, 7>(ctx, mdl, cd, P, S, B, x_guess, lam_guess, d, lbx, ubx, lbg, ubg, ss, qs, Hws, Aws, x, lam, info, stream, lds_limit, phase, &rst, slice_state, slice_iters)) return rst;
-        if (try_launch_reg<Model, 5>(ctx, mdl, cd, P, S, B, x_guess, lam_guess, d, lbx, ubx, lbg, ubg, ss, qs, Hws, Aws, x, lam, info, stream, lds_limit, phase, &rst, slice_state, slice_iters)) return rst;
-        if (try_launch_reg<Model, 11>(ctx, mdl, cd, P, S, B, x_guess, lam_guess, d, lbx, ubx, lbg, ubg, ss, qs, Hws, Aws, x, lam, info, stream, lds_limit, phase, &rst, slice_state, slice_iters)) return rst;   // config B / the reference's P = 5, S = 2 grids: 88..110 KKT rows
-        if constexpr (EXTRA_GRIDS<Model>::value) {   // 3-, 4-, 6-, 8-, 9-, 10-, 12- and 13-node grids of the built-in models
-            if (try_launch_extra_grids<Model>(ctx, mdl, cd, P, S, B, x_guess, lam_guess, d, lbx, ubx, lbg, ubg, ss, qs, Hws, Aws, x, lam, info, stream, lds_limit, phase, &rst, slice_state, slice_iters)) return rst;
+    if (ss->kkt_form == 2) { ss_default_form = *ss; ss_default_form.kkt_form = 0; ss = a.ss = &ss_default_form; }
+    SqpPlan<Model> plan;
+    bool planned = false;
+    if (!force_lds && ss->qp_solver == 0 && qs->linear_solver == 0) {   // (preconditioner / line_search = 1: the 7- and 11-node register kernels carry them, see plan_reg)
+        // node counts whose KKT system can fit 64 rows for small models (7 nodes: config A / D); 11: config B / the reference's P = 5, S = 2 grids (88..110 KKT rows)
+        planned = plan_reg<Model, 7>(ctx, a, plan) || plan_reg<Model, 5>(ctx, a, plan) || plan_reg<Model, 11>(ctx, a, plan);
+        if constexpr (EXTRA_GRIDS<Model>::value) planned = planned || plan_extra_grids<Model>(ctx, a, plan);   // 3-, 4-, 6-, 8-, 9-, 10-, 12- and 13-node grids of the built-in models
+    }
+    if (!planned) {
+        size_t lds = sqp_kernel_lds_bytes<Model>(P, S, SqpLdsLayout::LdsFactor, ss->qp_solver) + sqp_eig_lds_bytes<Model>(P, S, ss);
+        if (lds > lds_limit && ss->qp_solver == 1) return PMPC_ERR_UNSUPPORTED_SIZE;   // the stacked system lives in LDS only
+        if (lds > lds_limit && qs->linear_solver == 1) return PMPC_ERR_UNSUPPORTED_SIZE;   // the pivoted factorisation lives in LDS only
+        // Above BIG_KKT_MIN_ROWS rows the blocked tile factorisation (fp64 MFMA trailing updates, factor panels streamed from HBM / L2, 13 KB of LDS:
+        // one instance per SIMD) beats the LDS-resident triangle, whose footprint leaves one or two instances per CU — measured on robot grids, 2048
+        // instances: 104 rows 21.0 -> 18.3 ms, 128 rows (the reference's mpc_wrapper_test grid) 52.2 -> 25.3, 168 rows 247.6 -> 39.4; 72 rows 13.5 -> 17.7
+        // (stays in LDS). The stacked OSQP-form system and the pivoted factorisation exist in LDS only.
+        const bool prefer_big = dm.n + dm.m >= BIG_KKT_MIN_ROWS && ss->qp_solver == 0 && qs->linear_solver == 0 && !force_lds;
+        if (lds > lds_limit || prefer_big) {   // large instance: KKT factor in HBM, SQP / QP vectors in an HBM scratch behind it
+            lds = sqp_kernel_lds_bytes<Model>(P, S, SqpLdsLayout::HbmFactor) + sqp_eig_lds_bytes<Model>(P, S, ss);
+            if (lds > lds_limit) return PMPC_ERR_UNSUPPORTED_SIZE;
+            const size_t base16 = (base + 1) & ~(size_t)1;   // (16-byte boundary for the factor workspaces)
+            st = pmpc_internal_services(ctx, P, S, t0, tf, (base16 + (size_t)B * (BigKkt::doubles(dm.n + dm.m) + big_scratch_doubles<Model>(P, S))) * sizeof(double), &cdv, &ws, &streamv,
+                                        &a.lds_limit, &a.phase, &force_lds);
+            if (st != PMPC_OK) return st;
+            a.Hws = ws; a.Aws = ws + (size_t)B * dm.n * dm.n; a.slice_state = a.Aws + (size_t)B * dm.m * dm.n; plan.Kws = ws + base16;
+        }
+        phase = a.phase;
+        const bool hbm = plan.Kws != nullptr;
+        plan.route = hbm ? PMPC_ROUTE_HBM : PMPC_ROUTE_LDS;
+        plan.lds = lds;
+        plan.timed = true;
+        plan.kern = hbm ? sqp_kernel<Model, 0, 0, false, 0, true> : sqp_kernel<Model>;
+        // Mid-size instances on the HBM-factor kernel stream little per wavefront: with more instances than SIMDs a second wavefront per SIMD (a 256-register
+        // build of the same kernel) hides part of that latency — per 4096 robots 128 rows 40.5 -> 35.4 ms, 168 rows 64.3 -> 60.8; at config C's 464 rows
+        // the second wave only thrashes the L2 (2048 instances 93.0 -> 99.1 ms), hence the row bound.
+        if (hbm && dm.n + dm.m < BIG_TWO_WAVES_MAX_ROWS && B > pmpc_internal_simd_count(ctx) && !phase) plan.kern = sqp_kernel<Model, 0, 0, false, 0, true, true>;
+        // Small batches of large instances: a workgroup of four wavefronts per instance (BigTeam, pmpc_qp_big.hpp). With at most one instance per CU the chip is a
+        // quarter full at best on the one-wavefront kernel and the launch takes a lone instance's time; the team cuts that time (the condensed build, the blocked
+        // factorisation and the two triangular passes run on four SIMDs). Beyond BIG_WG4_MAX_BATCH instances the one-wavefront kernel's four instances per CU win.
+        // PMPC_BIG_WG4 = 0 / 1: developer switch (never / whenever eligible).
+        if constexpr (Model::NG == 0 && Model::NP == 0) {
+            const int wg4_on = pmpc_internal_switch(ctx, PMPC_SW_BIG_WG4_ON), wg4_off = pmpc_internal_switch(ctx, PMPC_SW_BIG_WG4_OFF);
+            const bool eligible = hbm && plan.kern == sqp_kernel<Model, 0, 0, false, 0, true> && ss->kkt_form == 0 && ss->preconditioner == 0 && ss->qp_solver == 0 && ss->regularisation != 1 &&
+                                  dm.n <= BIG_COND_MAX_ROWS && dm.m <= BIG_COND_MAX_ROWS && slice_iters == 0;
+            // Up to one instance per CU the team kernel may use the whole register file (512 per lane); from there to TWO instances per CU a second build of it,
+            // compiled for 256 registers so that two workgroups share a CU, still beats one wavefront per instance (kite-sized, 512 instances: 11.7 against 13.4 ms;
+            // the register diet costs it 4 % at 256 instances, hence two builds); beyond that the one-wavefront kernel's throughput wins (EXPERIMENTS.md round 5).
+            const int per_cu = BIG_WG4_MAX_BATCH * (pmpc_internal_simd_count(ctx) / 4) / 256;
+            const bool want = (wg4_on || wg4_off) ? (wg4_on != 0) : (B <= 2 * per_cu);
+            if (eligible && want) {
+                plan.kern = (B <= per_cu) ? sqp_kernel<Model, 0, 0, false, 0, true, false, false, false, true> : sqp_kernel<Model, 0, 0, false, 0, true, true, false, false, true>;
+                plan.threads = 4 * WAVE;
+            }
+        }
+        const bool team_kernel = plan.threads != WAVE;
+        if constexpr (LDS_PATH_PROFILED<Model>::value) {   // developer builds with phase timers
+            if (phase) {
+                plan.kern = hbm ? sqp_kernel<Model, 0, 0, true, 0, true> : sqp_kernel<Model, 0, 0, true>;
+                if constexpr (Model::NG == 0 && Model::NP == 0) { if (team_kernel) plan.kern = sqp_kernel<Model, 0, 0, true, 0, true, false, false, false, true>; }
+            }
+        } else if (phase && team_kernel) { plan.kern = sqp_kernel<Model, 0, 0, false, 0, true>; plan.threads = WAVE; }
+        if (hbm && ss->kkt_form == 0 && ss->qp_solver == 0 && !pmpc_internal_switch(ctx, PMPC_SW_NO_REDO_LAUNCH)) {
+            // redo launch (large-instance kernel, condensed mode): the instances whose QP gave up at its conditioning gate (PMPC_FLAG_ILLCOND; none on any
+            // BASELINE workload) are solved again, from their guesses, by the same kernel in the (n + m)-row KKT form
+            // (the two-wavefronts-per-SIMD build of the one-wavefront kernel: an instantiation of its own, so that a profile lists the redo launches — which
+            //  normally do nothing — on their own line instead of halving the large-instance kernel's averages; the full KKT form has no team version)
+            plan.redo = sqp_kernel<Model, 0, 0, false, 0, true, true>; plan.redo_lds = lds; plan.redo_full_form = true;
         }
     }
-    size_t lds = sqp_kernel_lds_bytes<Model>(P, S, 0, ss->qp_solver) + sqp_eig_lds_bytes<Model>(P, S, ss);
-    double* Kws = nullptr;
-    if (lds > lds_limit && ss->qp_solver == 1) return PMPC_ERR_UNSUPPORTED_SIZE;   // the stacked system lives in LDS only
-    if (lds > lds_limit && qs->linear_solver == 1) return PMPC_ERR_UNSUPPORTED_SIZE;   // the pivoted factorisation lives in LDS only
-    // Above BIG_KKT_MIN_ROWS rows the blocked tile factorisation (fp64 MFMA trailing updates, factor panels streamed from HBM / L2, 13 KB of LDS:
-    // one instance per SIMD) beats the LDS-resident triangle, whose footprint leaves one or two instances per CU — measured on robot grids, 2048
-    // instances: 104 rows 21.0 -> 18.3 ms, 128 rows (the reference's mpc_wrapper_test grid) 52.2 -> 25.3, 168 rows 247.6 -> 39.4; 72 rows 13.5 -> 17.7
-    // (stays in LDS). The stacked OSQP-form system and the pivoted factorisation exist in LDS only.
-    const bool prefer_big = dm.n + dm.m >= BIG_KKT_MIN_ROWS && ss->qp_solver == 0 && qs->linear_solver == 0 && !force_lds;
-    if (lds > lds_limit || prefer_big) {   // large instance: KKT factor in HBM, SQP / QP vectors in an HBM scratch behind it
-        lds = sqp_kernel_lds_bytes<Model>(P, S, 2) + sqp_eig_lds_bytes<Model>(P, S, ss);
-        if (lds > lds_limit) return PMPC_ERR_UNSUPPORTED_SIZE;
-        const size_t base16 = (base + 1) & ~(size_t)1;   // (16-byte boundary for the factor workspaces)
-        st = pmpc_internal_services(ctx, P, S, t0, tf, (base16 + (size_t)B * (BigKkt::doubles(dm.n + dm.m) + big_scratch_doubles<Model>(P, S))) * sizeof(double), &cdv, &ws, &streamv,
-                                    &lds_limit, &phase, &force_lds);
-        if (st != PMPC_OK) return st;
-        Hws = ws; Aws = ws + (size_t)B * dm.n * dm.n; slice_state = Aws + (size_t)B * dm.m * dm.n; Kws = ws + base16;
-    }
-    pmpc_internal_set_route(ctx, Kws ? PMPC_ROUTE_HBM : PMPC_ROUTE_LDS);
-    auto lkern = Kws ? sqp_kernel<Model, 0, 0, false, 0, true> : sqp_kernel<Model>;
-    // Mid-size instances on the HBM-factor kernel stream little per wavefront: with more instances than SIMDs a second wavefront per SIMD (a 256-register
-    // build of the same kernel) hides part of that latency — per 4096 robots 128 rows 40.5 -> 35.4 ms, 168 rows 64.3 -> 60.8; at config C's 464 rows
-    // the second wave only thrashes the L2 (2048 instances 93.0 -> 99.1 ms), hence the row bound.
-    if (Kws && dm.n + dm.m < BIG_TWO_WAVES_MAX_ROWS && B > pmpc_internal_simd_count(ctx) && !phase) lkern = sqp_kernel<Model, 0, 0, false, 0, true, true>;
-    // Small batches of large instances: a workgroup of four wavefronts per instance (BigTeam, pmpc_qp_big.hpp). With at most one instance per CU the chip is a
-    // quarter full at best on the one-wavefront kernel and the launch takes a lone instance's time; the team cuts that time (the condensed build, the blocked
-    // factorisation and the two triangular passes run on four SIMDs). Beyond BIG_WG4_MAX_BATCH instances the one-wavefront kernel's four instances per CU win.
-    // PMPC_BIG_WG4 = 0 / 1: developer switch (never / whenever eligible).
-    unsigned threads = WAVE;
-    if constexpr (Model::NG == 0 && Model::NP == 0) {
-        const int wg4_on = pmpc_internal_switch(ctx, PMPC_SW_BIG_WG4_ON), wg4_off = pmpc_internal_switch(ctx, PMPC_SW_BIG_WG4_OFF);
-        const bool eligible = Kws && lkern == sqp_kernel<Model, 0, 0, false, 0, true> && ss->kkt_form == 0 && ss->preconditioner == 0 && ss->qp_solver == 0 && ss->regularisation != 1 &&
-                              dm.n <= BIG_COND_MAX_ROWS && dm.m <= BIG_COND_MAX_ROWS && slice_iters == 0;
-        // Up to one instance per CU the team kernel may use the whole register file (512 per lane); from there to TWO instances per CU a second build of it,
-        // compiled for 256 registers so that two workgroups share a CU, still beats one wavefront per instance (kite-sized, 512 instances: 11.7 against 13.4 ms;
-        // the register diet costs it 4 % at 256 instances, hence two builds); beyond that the one-wavefront kernel's throughput wins (EXPERIMENTS.md round 5).
-        const int per_cu = BIG_WG4_MAX_BATCH * (pmpc_internal_simd_count(ctx) / 4) / 256;
-        const bool want = (wg4_on || wg4_off) ? (wg4_on != 0) : (B <= 2 * per_cu);
-        if (eligible && want) {
-            lkern = (B <= per_cu) ? sqp_kernel<Model, 0, 0, false, 0, true, false, false, false, true> : sqp_kernel<Model, 0, 0, false, 0, true, true, false, false, true>;
-            threads = 4 * WAVE;
-        }
-    }
-    const bool team_kernel = threads != WAVE;
-    if constexpr (LDS_PATH_PROFILED<Model>::value) {   // developer builds with phase timers
-        if (phase) {
-            lkern = Kws ? sqp_kernel<Model, 0, 0, true, 0, true> : sqp_kernel<Model, 0, 0, true>;
-            if constexpr (Model::NG == 0 && Model::NP == 0) { if (team_kernel) lkern = sqp_kernel<Model, 0, 0, true, 0, true, false, false, false, true>; }
-        }
-    } else if (phase && team_kernel) { lkern = sqp_kernel<Model, 0, 0, false, 0, true>; threads = WAVE; }
-    if (hipFuncSetAttribute((const void*)lkern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return PMPC_ERR_HIP;
-    const int slice = (slice_iters > 0) ? slice_iters : ss->max_iter;
-    for (int it = 0; it < ss->max_iter; it += slice)
-        hipLaunchKernelGGL(lkern, dim3(B), dim3(threads), lds, stream, mdl, cd, B, x_guess, lam_guess, d, lbx, ubx, lbg, ubg, *ss, *qs, Hws, Aws,
-                           x, lam, info, phase, Kws, it, it + slice, slice_state, (unsigned)(lds / sizeof(double)));
-    if (Kws && ss->kkt_form == 0 && ss->qp_solver == 0 && !pmpc_internal_switch(ctx, PMPC_SW_NO_REDO_LAUNCH)) {
-        // redo launch (large-instance kernel, condensed mode): the instances whose QP gave up at its conditioning gate (PMPC_FLAG_ILLCOND; none on any
-        // BASELINE workload) are solved again, from their guesses, by the same kernel in the (n + m)-row KKT form — every other workgroup reads one word and exits
-        pmpc_sqp_settings ss_full = *ss; ss_full.kkt_form = 1;
-        // (the two-wavefronts-per-SIMD build of the one-wavefront kernel: an instantiation of its own, so that a profile lists the redo launches — which
-        //  normally do nothing — on their own line instead of halving the large-instance kernel's averages; the full KKT form has no team version)
-        auto rkern = sqp_kernel<Model, 0, 0, false, 0, true, true>;
-        if (hipFuncSetAttribute((const void*)rkern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return PMPC_ERR_HIP;
-        hipLaunchKernelGGL(rkern, dim3(B), dim3(WAVE), lds, stream, mdl, cd, B, x_guess, lam_guess, d, lbx, ubx, lbg, ubg, ss_full, *qs, Hws, Aws,
-                           x, lam, info, (unsigned long long*)nullptr, Kws, PMPC_REDO_MODE, ss->max_iter, (double*)nullptr, (unsigned)(lds / sizeof(double)));
-    }
-    return (hipGetLastError() == hipSuccess) ? PMPC_OK : PMPC_ERR_HIP;
+    return launch_sqp_plan(ctx, plan, a);
 }
 
 }  // namespace pmpc

@@ -9,7 +9,7 @@
 #define MODEL pmpc::ParkingOCP
 namespace pmpc {
 template <> bool try_launch_schur_grids<MODEL>(PMPC_SCHUR_ARGS) {
-    if (ss->kkt_form != 2) return false;
+    if (a.ss->kkt_form != 2) return false;
     PMPC_SCHUR_TRY(5, 2)
     return false;
 }

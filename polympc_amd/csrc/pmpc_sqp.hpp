@@ -76,15 +76,10 @@ struct SqpDevice {
     // History of the condensed kernels (PS = -1): until late round 6 the launcher never routed preconditioner = 1 to them (Ruiz rescales the workspace the per-node blocks of A mirror),
     // the calls were dead code there — and in round 4 / 5 they were what MISCOMPILED the hook build of the small condensed kernel (robot 11 nodes, 55 + 33, one row per lane: with the three
     // never-executed calls compiled in, the QP step of the primal-only lanes was lost — a VGPR -> AGPR copy of the lane id placed inside a partial-EXEC block, DESIGN.md hazard 3 /
-    // EXPERIMENTS.md round 6), so round 5 compiled them out. -DPMPC_EXPERIMENT_CND_WITH_RUIZ restores exactly that round-5 build (developer switch: reproduces the fault on hipcc 7.2
-    // when the allocator makes the same choice).
-#ifdef PMPC_EXPERIMENT_CND_WITH_RUIZ
-    static constexpr bool RUIZ_COMPILED = HOOKS && (int)Dm::NDER <= RUIZ_MAX_NDER;
-#else
+    // EXPERIMENTS.md round 6), so round 5 compiled them out.
     // (late round 6: the hook builds of the condensed kernels carry the Ruiz calls again — their tables come from the scaled workspace, pmpc_qp_cond.hpp WS; the fault of round 5 is one
     //  the CPU suite now detects in the built code, tests/test_kernel_occupancy_cpu.py)
     static constexpr bool RUIZ_COMPILED = HOOKS && (int)Dm::NDER <= RUIZ_MAX_NDER && PS <= 0;   // (PS > 0: the block-structured kernel has no dense workspace to scale — of the hooks it carries the filter line search only)
-#endif
     static constexpr bool REG1 = !SCH && NN > 0 && NN + MM <= WAVE;    // one KKT row per lane
     static constexpr bool REG2 = !SCH && NN > 0 && NN + MM > WAVE;     // two KKT rows per lane
     double *hblk = nullptr, *hbrd = nullptr /* NP = 1: border row + corner, border column (pmpc_qp_schur.hpp) */, *qblk = nullptr, *xsc = nullptr, *dsc = nullptr, *dtab = nullptr;   // SCH: Hessian blocks, Q blocks, the exchange vectors and the D~ tables of the QP (LDS)

@@ -164,7 +164,7 @@ def test_exec_window_helpers_start_with_every_lane_enabled_and_no_spill_loses_la
     (2) What that fault really was — compiler hazard 3 of DESIGN.md, now with the instruction sequence: a VGPR -> AGPR spill (`v_accvgpr_write_b32 a116, v40`,
         the lane id) emitted inside the else-block of a lane-divergent if / else and read back at full EXEC; the lanes of the then-side come back as stale
         register content. Here: no accumulation register of any shipped kernel is written under a provably narrowed EXEC and read back with provably more
-        lanes enabled (the faulty build: three such reads in exactly the faulty kernel, tests/experiments/exec_probe_run.sh). The same rule over the private
+        lanes enabled (the faulty build: three such reads in exactly the faulty kernel; its probe script was removed, see git history). The same rule over the private
         (scratch) slots with a constant offset — the other place a spill can go: about 10 000 spill stores and 17 000 reloads in the library, none of them loses lanes."""
     from concurrent.futures import ProcessPoolExecutor
     with tempfile.TemporaryDirectory() as tmp:
