@@ -795,3 +795,187 @@ template <typename A> struct device_binding<models::CSTR<A>> {
     }
 };
 }  // namespace polympc
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Generic NLPs: the reference's ProblemBase problems (src/solvers/nlproblem.hpp) and the SQP solver surface its own SQP tests use
+// (tests/solvers/sqp/sqp_test_autodiff.cpp). The problem's device code is either built into libpolympc_amd.so (POLYMPC_USE_BUILTIN_NLP)
+// or compiled by hipcc with PMPC_REGISTER_NLP (register_nlp.hpp) and bound with POLYMPC_USE_REGISTERED_NLP. The reference's solver class
+// that installs eigenvalue mirroring (hessian_regularisation_dense_impl) corresponds to settings().regularisation = 1 here.
+namespace polympc {
+template <typename Derived> struct nlp_traits;
+#define POLYMPC_FORWARD_NLP_DECLARATION(cNAME, cNX, cNE, cNI, cNP, TYPE) \
+    class cNAME;                                                         \
+    template <> struct polympc::nlp_traits<cNAME> {                      \
+        using Scalar = TYPE;                                             \
+        enum { NX = cNX, NE = cNE, NI = cNI, NP = cNP };                 \
+    };
+
+template <typename NLP> struct nlp_device_binding;   // specialised by POLYMPC_USE_BUILTIN_NLP / POLYMPC_USE_REGISTERED_NLP
+
+// sizes and types of ProblemBase (nlproblem.hpp); the cost / constraint templates live in device code
+template <typename Derived>
+class ProblemBase {
+public:
+    using scalar_t = typename nlp_traits<Derived>::Scalar;
+    enum { VAR_SIZE = nlp_traits<Derived>::NX, NUM_EQ = nlp_traits<Derived>::NE, NUM_INEQ = nlp_traits<Derived>::NI,
+           NUM_CONSTR = nlp_traits<Derived>::NE + nlp_traits<Derived>::NI, DUAL_SIZE = NUM_CONSTR + VAR_SIZE, NP = nlp_traits<Derived>::NP };
+    using nlp_variable_t = Vector<VAR_SIZE>;
+    using nlp_dual_t = Vector<DUAL_SIZE>;
+    using nlp_eq_constraints_t = Vector<NUM_EQ>;
+    using nlp_ineq_constraints_t = Vector<NUM_INEQ>;
+    using static_parameter_t = Vector<NP>;
+};
+
+// B independent instances of NlpSolver<Problem> solved by one kernel launch
+template <typename Problem>
+class NlpBatchSolver {
+public:
+    enum { VAR_SIZE = Problem::VAR_SIZE, NUM_EQ = Problem::NUM_EQ, NUM_INEQ = Problem::NUM_INEQ, DUAL_SIZE = Problem::DUAL_SIZE, NP = Problem::NP };
+    explicit NlpBatchSolver(int batch) : B(batch) {
+        const double INF = std::numeric_limits<double>::infinity();
+        m_x.assign((size_t)B * VAR_SIZE, 0.0); m_lam.assign((size_t)B * DUAL_SIZE, 0.0);
+        m_lbx.assign((size_t)B * VAR_SIZE, -INF); m_ubx.assign((size_t)B * VAR_SIZE, INF);
+        m_lbg.assign((size_t)B * NUM_INEQ, -INF); m_ubg.assign((size_t)B * NUM_INEQ, INF);
+        m_p.assign((size_t)B * (NP > 0 ? NP : 1), 0.0);
+        m_info.resize(B);
+        pmpc_qp_settings_sqp_default(&m_qp_settings);   // SQPBase constructor overrides, sqp_base.hpp:83-90
+    }
+    int batch() const { return B; }
+    Problem& get_problem() noexcept { return problem; }
+    sqp_settings_t& settings() noexcept { return m_settings; }
+    qp_solver_settings_t& qp_settings() noexcept { return m_qp_settings; }
+    double* primal_solution(int b) noexcept { return &m_x[(size_t)b * VAR_SIZE]; }
+    double* dual_solution(int b) noexcept { return &m_lam[(size_t)b * DUAL_SIZE]; }
+    double* lower_bound_x(int b) noexcept { return &m_lbx[(size_t)b * VAR_SIZE]; }
+    double* upper_bound_x(int b) noexcept { return &m_ubx[(size_t)b * VAR_SIZE]; }
+    double* lower_bound_g(int b) noexcept { return &m_lbg[(size_t)b * NUM_INEQ]; }
+    double* upper_bound_g(int b) noexcept { return &m_ubg[(size_t)b * NUM_INEQ]; }
+    double* parameters(int b) noexcept { return &m_p[(size_t)b * (NP > 0 ? NP : 1)]; }
+    const pmpc_sqp_info& info(int b) const noexcept { return m_info[b]; }
+
+    // SQPBase::solve for every instance; the current primal / dual arrays are the initial guess
+    pmpc_status solve() noexcept {
+        pmpc_context* ctx = context();
+        if (!ctx) return last_error();
+        if (m_settings.line_search != 0 || m_settings.iteration_callback != nullptr) return last_error() = PMPC_ERR_INVALID_ARGUMENT;   // not on this route
+        pmpc_sqp_settings ss;
+        pmpc_sqp_settings_default(&ss);
+        ss.tau = m_settings.tau; ss.eta = m_settings.eta; ss.rho = m_settings.rho; ss.eps_prim = m_settings.eps_prim;
+        ss.eps_dual = m_settings.eps_dual; ss.max_iter = m_settings.max_iter; ss.line_search_max_iter = m_settings.line_search_max_iter;
+        ss.regularisation = m_settings.regularisation; ss.exact_hessian_every_iter = m_settings.exact_hessian_every_iter ? 1 : 0;
+        ss.preconditioner = m_settings.preconditioner; ss.hessian_update = m_settings.hessian_update; ss.qp_solver = m_settings.qp_solver;
+        ss.kkt_form = m_settings.kkt_form;
+        std::vector<double> xo(m_x.size()), lo(m_lam.size());
+        const pmpc_status st = nlp_device_binding<Problem>::solve(ctx, problem, B, m_x.data(), m_lam.data(), NP > 0 ? m_p.data() : nullptr, m_lbx.data(),
+                                                                  m_ubx.data(), NUM_INEQ > 0 ? m_lbg.data() : nullptr, NUM_INEQ > 0 ? m_ubg.data() : nullptr,
+                                                                  &ss, &m_qp_settings, xo.data(), lo.data(), m_info.data());
+        last_error() = st;
+        if (st == PMPC_OK) { m_x.swap(xo); m_lam.swap(lo); }
+        return st;
+    }
+
+    Problem problem;
+    int B;
+    std::vector<double> m_x, m_lam, m_lbx, m_ubx, m_lbg, m_ubg, m_p;
+    std::vector<pmpc_sqp_info> m_info;
+    sqp_settings_t m_settings;
+    qp_solver_settings_t m_qp_settings;
+};
+
+// NlpSolver<Problem>: the single-instance surface of SQPBase that sqp_test_autodiff.cpp uses (sqp_base.hpp:159-195, :368-374)
+template <typename Problem>
+class NlpSolver {
+public:
+    enum { VAR_SIZE = Problem::VAR_SIZE, NUM_EQ = Problem::NUM_EQ, NUM_INEQ = Problem::NUM_INEQ, DUAL_SIZE = Problem::DUAL_SIZE, NP = Problem::NP };
+    using scalar_t = double;
+    using nlp_variable_t = typename Problem::nlp_variable_t;
+    using nlp_dual_t = typename Problem::nlp_dual_t;
+    using nlp_ineq_constraints_t = typename Problem::nlp_ineq_constraints_t;
+    using parameter_t = typename Problem::static_parameter_t;
+    using nlp_settings_t = sqp_settings_t;
+    using nlp_info_t = sqp_info_t;
+
+    NlpSolver() : m_batch(1) {
+        const double INF = std::numeric_limits<double>::infinity();
+        m_lbx = nlp_variable_t::Constant(-INF); m_ubx = nlp_variable_t::Constant(INF);
+        m_lbg = nlp_ineq_constraints_t::Constant(-INF); m_ubg = nlp_ineq_constraints_t::Constant(INF);
+        m_x.setZero(); m_lam.setZero(); m_p.setZero();
+    }
+    const Problem& get_problem() const noexcept { return m_batch.problem; }
+    Problem& get_problem() noexcept { return m_batch.problem; }
+    const nlp_variable_t& primal_solution() const noexcept { return m_x; }
+    nlp_variable_t& primal_solution() noexcept { return m_x; }
+    const nlp_dual_t& dual_solution() const noexcept { return m_lam; }
+    nlp_dual_t& dual_solution() noexcept { return m_lam; }
+    nlp_settings_t& settings() noexcept { return m_batch.settings(); }
+    qp_solver_settings_t& qp_settings() noexcept { return m_batch.qp_settings(); }
+    const sqp_info_t& info() const noexcept { return m_info; }
+    nlp_variable_t& lower_bound_x() noexcept { return m_lbx; }
+    nlp_variable_t& upper_bound_x() noexcept { return m_ubx; }
+    nlp_ineq_constraints_t& lower_bound_g() noexcept { return m_lbg; }
+    nlp_ineq_constraints_t& upper_bound_g() noexcept { return m_ubg; }
+    parameter_t& parameters() noexcept { return m_p; }
+    double primal_norm() const noexcept { return m_primal_norm; }
+    double dual_norm() const noexcept { return m_dual_norm; }
+    double constr_violation() const noexcept { return m_max_violation; }
+    double cost() const noexcept { return m_cost; }
+    /** not in the reference: the device's information word for the last solve (PMPC_FLAG_NONFINITE, PMPC_FLAG_ILLCOND; include/polympc_amd.h) */
+    int info_flags() const noexcept { return m_batch.info(0).flags; }
+
+    void solve() noexcept {
+        std::copy(m_x.data(), m_x.data() + VAR_SIZE, m_batch.primal_solution(0));
+        std::copy(m_lam.data(), m_lam.data() + DUAL_SIZE, m_batch.dual_solution(0));
+        std::copy(m_lbx.data(), m_lbx.data() + VAR_SIZE, m_batch.lower_bound_x(0));
+        std::copy(m_ubx.data(), m_ubx.data() + VAR_SIZE, m_batch.upper_bound_x(0));
+        std::copy(m_lbg.data(), m_lbg.data() + NUM_INEQ, m_batch.lower_bound_g(0));
+        std::copy(m_ubg.data(), m_ubg.data() + NUM_INEQ, m_batch.upper_bound_g(0));
+        std::copy(m_p.data(), m_p.data() + NP, m_batch.parameters(0));
+        m_info.status.value = sqp_status_t::MAX_ITER_EXCEEDED;
+        if (m_batch.solve() != PMPC_OK) { m_info.status.value = sqp_status_t::INVALID_SETTINGS; return; }
+        std::copy(m_batch.primal_solution(0), m_batch.primal_solution(0) + VAR_SIZE, m_x.data());
+        std::copy(m_batch.dual_solution(0), m_batch.dual_solution(0) + DUAL_SIZE, m_lam.data());
+        const pmpc_sqp_info& i = m_batch.info(0);
+        m_info.iter = i.iter; m_info.qp_solver_iter = i.qp_solver_iter;
+        m_info.status.value = i.status == PMPC_SQP_SOLVED ? sqp_status_t::SOLVED : sqp_status_t::MAX_ITER_EXCEEDED;
+        m_primal_norm = i.primal_norm; m_dual_norm = i.dual_norm; m_max_violation = i.max_violation; m_cost = i.cost;
+    }
+    void solve(const nlp_variable_t& x_guess, const nlp_dual_t& lam_guess) noexcept { m_x = x_guess; m_lam = lam_guess; solve(); }
+
+    nlp_variable_t m_x, m_lbx, m_ubx;
+    nlp_dual_t m_lam;
+    nlp_ineq_constraints_t m_lbg, m_ubg;
+    parameter_t m_p;
+    sqp_info_t m_info;
+    double m_primal_norm = 0, m_dual_norm = 0, m_max_violation = 0, m_cost = 0;
+private:
+    NlpBatchSolver<Problem> m_batch;
+};
+
+// PROBLEM_ID: a pmpc_nlp_problem (the NLPs of sqp_test_autodiff.cpp built into the library)
+#define POLYMPC_USE_BUILTIN_NLP(Name, PROBLEM_ID)                                                                                      \
+    template <> struct polympc::nlp_device_binding<Name> {                                                                             \
+        static pmpc_status solve(pmpc_context* ctx, const Name&, int B, const double* xg, const double* lg, const double* d,         \
+                                 const double* lbx, const double* ubx, const double* lbg, const double* ubg, const pmpc_sqp_settings* ss, \
+                                 const pmpc_qp_settings* qs, double* x, double* lam, pmpc_sqp_info* info) {                          \
+            return pmpc_nlp_solve_batch(ctx, PROBLEM_ID, B, xg, lg, d, lbx, ubx, lbg, ubg, ss, qs, x, lam, info);                     \
+        }                                                                                                                              \
+    };
+
+// DeviceNLP = the struct registered with PMPC_REGISTER_NLP in the .hip translation unit; the host problem class exposes
+// `DeviceNLP device_problem() const` returning the object that is copied into the kernel.
+#define POLYMPC_USE_REGISTERED_NLP(Name, DeviceNLP)                                                                                    \
+    extern "C" pmpc_status pmpc_user_nlp_sqp_dev_##DeviceNLP(pmpc_context*, const void*, int, const double*, const double*,          \
+                                                             const double*, const double*, const double*, const double*,             \
+                                                             const double*, const pmpc_sqp_settings*, const pmpc_qp_settings*,       \
+                                                             double*, double*, pmpc_sqp_info*);                                      \
+    template <> struct polympc::nlp_device_binding<Name> {                                                                             \
+        static pmpc_status solve(pmpc_context* ctx, const Name& nlp, int B, const double* xg, const double* lg, const double* d,     \
+                                 const double* lbx, const double* ubx, const double* lbg, const double* ubg, const pmpc_sqp_settings* ss, \
+                                 const pmpc_qp_settings* qs, double* x, double* lam, pmpc_sqp_info* info) {                          \
+            const auto dp = nlp.device_problem();                                                                                      \
+            return pmpc_nlp_solve_batch_user(ctx, pmpc_user_nlp_sqp_dev_##DeviceNLP, &dp, Name::VAR_SIZE, Name::NUM_EQ, Name::NUM_INEQ, \
+                                             Name::NP, B, xg, lg, d, lbx, ubx, lbg, ubg, ss, qs, x, lam, info);                      \
+        }                                                                                                                              \
+    };
+
+}  // namespace polympc

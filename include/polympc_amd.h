@@ -387,6 +387,47 @@ pmpc_status pmpc_sqp_solve_batch_user(pmpc_context* ctx, pmpc_sqp_dev_fn fn, con
                                       const double* lbg, const double* ubg, const pmpc_sqp_settings* sqp_settings,
                                       const pmpc_qp_settings* qp_settings, double* x, double* lam, pmpc_sqp_info* info);
 
+/* ---- generic NLPs ----------------------------------------------------------------------------------------------------
+ * Batched SQPBase::solve for NLPs that are not collocation OCPs: the reference's ProblemBase problems (src/solvers/nlproblem.hpp), with
+ * NX variables, NE equalities, NI inequalities and NP static parameters (POLYMPC_FORWARD_NLP_DECLARATION, nlproblem.hpp:26-34). One
+ * wavefront per instance, every vector and matrix of the iteration in LDS, NX + NE + NI <= 64 KKT rows (PMPC_ERR_UNSUPPORTED_SIZE beyond).
+ * Linearisation by forward AD; dense damped BFGS or exact_hessian_every_iter; regularisation 0 / 1 / 2; the QP is the one-row-per-lane
+ * register box-ADMM with its numeric conditioning gate — an instance whose QP trips the gate stops there with status 4 and
+ * PMPC_FLAG_ILLCOND (no full-form re-solve exists on this route); the l1-merit line search and termination test of the OCP kernels.
+ * Settings this route does not implement are refused with PMPC_ERR_INVALID_ARGUMENT before anything is launched: hessian_update,
+ * qp_solver, preconditioner, line_search, kkt_form other than 0, a non-NULL filter_state or iteration_trace, qp linear_solver other than 0.
+ * Layouts (instance-major, fp64): x B*NX, lam B*(NE+NI+NX) = [eq | ineq | box], d B*NP, lbx/ubx B*NX, lbg/ubg B*NI. Every input may be NULL:
+ * x_guess, lam_guess and d are then zeros, lbx / lbg -inf and ubx / ubg +inf.
+ * Built-in problems (ids as the checker's ORC_NLP_*): the four NLPs of tests/solvers/sqp/sqp_test_autodiff.cpp. User problems are compiled
+ * with PMPC_REGISTER_NLP(Name) (include/polympc/register_nlp.hpp). */
+typedef enum { PMPC_NLP_CONSTRAINED_ROSENBROCK = 0, PMPC_NLP_ROSENBROCK = 1, PMPC_NLP_SIMPLE = 2, PMPC_NLP_HS071 = 3 } pmpc_nlp_problem;
+pmpc_status pmpc_nlp_dims(int problem, int* nx, int* ne, int* ni, int* np);
+/* GenericNLP::lagrangian_gradient_hessian at B points (host buffers; any output may be NULL; lam NULL = zeros; d may be NULL only when NP = 0):
+ * cost B, constr B*(NE+NI) = [eq | ineq], jac B*(NE+NI)*NX (column-major per instance), cost_grad B*NX, lag_grad B*NX, lag_hess B*NX*NX
+ * (column-major per instance). */
+pmpc_status pmpc_nlp_linearise_batch(pmpc_context* ctx, int problem, int B, const double* x, const double* lam, const double* d, double* cost,
+                                     double* constr, double* jac, double* cost_grad, double* lag_grad, double* lag_hess);
+/* Host buffers. */
+pmpc_status pmpc_nlp_solve_batch(pmpc_context* ctx, int problem, int B, const double* x_guess, const double* lam_guess, const double* d,
+                                 const double* lbx, const double* ubx, const double* lbg, const double* ubg, const pmpc_sqp_settings* sqp_settings,
+                                 const pmpc_qp_settings* qp_settings, double* x, double* lam, pmpc_sqp_info* info);
+/* Device buffers; asynchronous on the context's stream. */
+pmpc_status pmpc_nlp_solve_batch_dev(pmpc_context* ctx, int problem, int B, const double* x_guess, const double* lam_guess, const double* d,
+                                     const double* lbx, const double* ubx, const double* lbg, const double* ubg,
+                                     const pmpc_sqp_settings* sqp_settings, const pmpc_qp_settings* qp_settings, double* x, double* lam,
+                                     pmpc_sqp_info* info);
+/* A registered problem's solve on device buffers (the symbol pmpc_user_nlp_sqp_dev_<Name> that PMPC_REGISTER_NLP emits); `model` points to
+ * the user's problem object (copied by value into the kernel). pmpc_nlp_solve_batch_user is the matching host-buffer wrapper, given the
+ * problem's dimensions (pmpc_user_nlp_dims_<Name>). */
+typedef pmpc_status (*pmpc_nlp_dev_fn)(pmpc_context* ctx, const void* model, int B, const double* x_guess, const double* lam_guess,
+                                       const double* d, const double* lbx, const double* ubx, const double* lbg, const double* ubg,
+                                       const pmpc_sqp_settings* sqp_settings, const pmpc_qp_settings* qp_settings, double* x, double* lam,
+                                       pmpc_sqp_info* info);
+pmpc_status pmpc_nlp_solve_batch_user(pmpc_context* ctx, pmpc_nlp_dev_fn fn, const void* model, int nx, int ne, int ni, int np, int B,
+                                      const double* x_guess, const double* lam_guess, const double* d, const double* lbx, const double* ubx,
+                                      const double* lbg, const double* ubg, const pmpc_sqp_settings* sqp_settings,
+                                      const pmpc_qp_settings* qp_settings, double* x, double* lam, pmpc_sqp_info* info);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,6 +16,9 @@ SQP_SOLVED, SQP_MAX_ITER_EXCEEDED = 0, 1
 FLAG_NONFINITE = 1   # pmpc_qp_info / pmpc_sqp_info flags: a non-finite value went through a QP solve
 FLAG_ILLCOND = 2     # the conditioning gate of the constraint-first / condensed kernels tripped: solved in the full KKT form (information)
 
+NLP_CONSTRAINED_ROSENBROCK, NLP_ROSENBROCK, NLP_SIMPLE, NLP_HS071 = 0, 1, 2, 3   # pmpc_nlp_problem: the NLPs of sqp_test_autodiff.cpp
+NLP_ILLCOND_STOP = 4   # pmpc_sqp_info status on the NLP route: a QP tripped the conditioning gate and the instance stopped (flag FLAG_ILLCOND)
+
 ABI_VERSION = 4   # PMPC_ABI_VERSION of include/polympc_amd.h that the ctypes layouts below mirror
 ROUTE_NONE, ROUTE_REG1, ROUTE_REG2, ROUTE_LDS, ROUTE_HBM, ROUTE_SCHUR, ROUTE_CONDREG = 0, 1, 2, 3, 4, 5, 6   # pmpc_route
 ROUTE_NAMES = {0: "none", 1: "reg1", 2: "reg2", 3: "lds", 4: "hbm", 5: "schur", 6: "condreg"}
@@ -30,6 +33,7 @@ EXPORTED_SYMBOLS = [
     "pmpc_qp_admm_solve_batch", "pmpc_qp_admm_solve_batch_dev", "pmpc_qp_ruiz_compute_batch", "pmpc_qp_ruiz_compute_batch_dev", "pmpc_qp_ruiz_unscale_batch", "pmpc_qp_ruiz_unscale_batch_dev",
     "pmpc_filter_state_create", "pmpc_filter_state_clear", "pmpc_filter_state_download", "pmpc_filter_state_destroy",
     "pmpc_iteration_trace_create", "pmpc_iteration_trace_clear", "pmpc_iteration_trace_download", "pmpc_iteration_trace_destroy",
+    "pmpc_nlp_dims", "pmpc_nlp_linearise_batch", "pmpc_nlp_solve_batch", "pmpc_nlp_solve_batch_dev", "pmpc_nlp_solve_batch_user",
 ]
 
 
@@ -161,6 +165,66 @@ def ocp_dims(model, P, S):
     _check(lib().pmpc_ocp_dims(model, P, S, *[C.byref(a) for a in v]))
     nx, nu, np_, nd, ng, n, me, mi = [a.value for a in v]
     return dict(nx=nx, nu=nu, np=np_, nd=nd, ng=ng, n=n, m_eq=me, m_ineq=mi, m=me + mi, nn=P * S + 1)
+
+
+class StatusError(RuntimeError):
+    """a pmpc_status other than PMPC_OK, kept in .status"""
+
+    def __init__(self, st):
+        super().__init__("polympc_amd: " + lib().pmpc_status_string(st).decode())
+        self.status = st
+
+
+def _check_status(st):
+    if st != 0:
+        raise StatusError(st)
+
+
+def nlp_dims(problem):
+    """dimensions of a built-in NLP: dict(nx, ne, ni, np, m = ne + ni)"""
+    v = [C.c_int() for _ in range(4)]
+    _check_status(lib().pmpc_nlp_dims(int(problem), *[C.byref(a) for a in v]))
+    nx, ne, ni, np_ = [a.value for a in v]
+    return dict(nx=nx, ne=ne, ni=ni, np=np_, m=ne + ni)
+
+
+_NLP_SOLVE_ARGTYPES = [C.POINTER(C.c_double)] * 7 + [C.POINTER(SQPSettings), C.POINTER(QPSettings), C.POINTER(C.c_double),
+                                                     C.POINTER(C.c_double), C.c_void_p]
+
+
+def _nlp_host_call(f, lead, B, dims, x_guess, lam_guess, d, lbx, ubx, lbg, ubg, sqp_settings, qp_settings):
+    """the host-buffer NLP solves: shared staging of the optional inputs and the outputs"""
+    nx, m = dims["nx"], dims["m"]
+    ss = sqp_settings or sqp_settings_default(); qs = qp_settings or qp_settings_sqp_default()
+    x = np.zeros((B, nx)); lam = np.zeros((B, m + nx)); info = np.zeros(B, dtype=SQP_INFO_DTYPE)
+    keep = [_h(a) for a in (x_guess, lam_guess, d, lbx, ubx, lbg, ubg)]
+    P_ = C.POINTER(C.c_double)
+    _check_status(f(*lead, int(B), *[k[1] for k in keep], C.byref(ss), C.byref(qs), x.ctypes.data_as(P_), lam.ctypes.data_as(P_),
+                    C.c_void_p(info.ctypes.data)))
+    return x, lam, info
+
+
+class UserNLP:
+    """A problem registered with PMPC_REGISTER_NLP(name) in a user's shared library: its dimensions and its batched solve
+    (pmpc_nlp_solve_batch_user with the library's pmpc_user_nlp_sqp_dev_<name>). `model` is the bytes of the user's problem object
+    (copied by value into the kernel; default: 8 zero bytes, for a class without data members)."""
+
+    def __init__(self, so_path, name, model=None):
+        self.so = C.CDLL(os.path.abspath(so_path))
+        self.fn = getattr(self.so, "pmpc_user_nlp_sqp_dev_" + name)
+        v = [C.c_int() for _ in range(4)]
+        getattr(self.so, "pmpc_user_nlp_dims_" + name)(*[C.byref(a) for a in v])
+        nx, ne, ni, np_ = [a.value for a in v]
+        self.dims = dict(nx=nx, ne=ne, ni=ni, np=np_, m=ne + ni)
+        self.model = C.create_string_buffer(bytes(model) if model is not None else bytes(8))
+
+    def solve_batch(self, ctx, B, x_guess=None, lam_guess=None, d=None, lbx=None, ubx=None, lbg=None, ubg=None, sqp_settings=None,
+                    qp_settings=None):
+        f = lib().pmpc_nlp_solve_batch_user
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 5 + _NLP_SOLVE_ARGTYPES
+        dm = self.dims
+        lead = (ctx._ctx, C.cast(self.fn, C.c_void_p), C.cast(self.model, C.c_void_p), dm["nx"], dm["ne"], dm["ni"], dm["np"])
+        return _nlp_host_call(f, lead, B, dm, x_guess, lam_guess, d, lbx, ubx, lbg, ubg, sqp_settings, qp_settings)
 
 
 def _h(a):
@@ -384,6 +448,39 @@ class Context:
                  C.byref(sqp_settings), C.byref(qp_settings), _d(x), _d(lam), C.c_void_p(info.data_ptr()), _d(u0)))
 
     # ------------------------------------------------------------------ SQP, device buffers (torch tensors), asynchronous
+    # ------------------------------------------------------------------ generic NLPs (pmpc_nlp_*)
+    def nlp_linearise_batch(self, problem, x, lam=None, d=None):
+        """GenericNLP::lagrangian_gradient_hessian at the rows of x: dict(cost (B,), c (B, m), jac (B, m, nx), cost_grad, lag_grad (B, nx),
+        lag_hess (B, nx, nx))"""
+        dm = nlp_dims(problem); nx, m = dm["nx"], dm["m"]
+        xk, xp = _h(np.atleast_2d(x)); B = xk.shape[0]
+        lk, lp = _h(lam); dk, dp_ = _h(d)
+        cost = np.zeros(B); c = np.zeros((B, max(m, 1))); jac = np.zeros((B, max(m, 1) * nx)); cg = np.zeros((B, nx)); lg = np.zeros((B, nx))
+        lh = np.zeros((B, nx * nx))
+        P_ = C.POINTER(C.c_double)
+        f = lib().pmpc_nlp_linearise_batch
+        f.argtypes = [C.c_void_p, C.c_int, C.c_int] + [P_] * 9
+        _check_status(f(self._ctx, int(problem), B, xp, lp, dp_, *[a.ctypes.data_as(P_) for a in (cost, c, jac, cg, lg, lh)]))
+        return dict(cost=cost, c=c[:, :m], jac=jac[:, :m * nx].reshape(B, nx, m).transpose(0, 2, 1).copy(), cost_grad=cg, lag_grad=lg,
+                    lag_hess=lh.reshape(B, nx, nx).transpose(0, 2, 1).copy())
+
+    def nlp_solve_batch(self, problem, B, x_guess=None, lam_guess=None, d=None, lbx=None, ubx=None, lbg=None, ubg=None, sqp_settings=None,
+                        qp_settings=None):
+        """pmpc_nlp_solve_batch (host buffers) -> x (B, nx), lam (B, m + nx), info (SQP_INFO_DTYPE); None inputs take the defaults of the
+        C entry point (zeros; -inf / +inf bounds)"""
+        f = lib().pmpc_nlp_solve_batch
+        f.argtypes = [C.c_void_p, C.c_int, C.c_int] + _NLP_SOLVE_ARGTYPES
+        return _nlp_host_call(f, (self._ctx, int(problem)), B, nlp_dims(problem), x_guess, lam_guess, d, lbx, ubx, lbg, ubg, sqp_settings,
+                              qp_settings)
+
+    def nlp_solve_batch_dev(self, problem, B, x, lam, info, sqp_settings, qp_settings, x_guess=None, lam_guess=None, d=None, lbx=None, ubx=None,
+                            lbg=None, ubg=None):
+        """pmpc_nlp_solve_batch_dev on torch CUDA tensors (info: a uint8 tensor of B * 48 bytes); asynchronous on the context's stream"""
+        f = lib().pmpc_nlp_solve_batch_dev
+        f.argtypes = [C.c_void_p, C.c_int, C.c_int] + _NLP_SOLVE_ARGTYPES
+        _check_status(f(self._ctx, int(problem), int(B), _d(x_guess), _d(lam_guess), _d(d), _d(lbx), _d(ubx), _d(lbg), _d(ubg),
+                        C.byref(sqp_settings), C.byref(qp_settings), _d(x), _d(lam), C.c_void_p(info.data_ptr())))
+
     def sqp_solve_batch_dev(self, model, P, S, t0, tf, B, d, lbx, ubx, x, lam, info, sqp_settings, qp_settings, lbg=None,
                             ubg=None, x_guess=None, lam_guess=None, mparams=None):
         mk, mp = _h(mparams)
