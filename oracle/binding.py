@@ -28,6 +28,11 @@ def _check_sweep(pivot, rows):
         raise ValueError(f"PIVOT_SWEEP2 supports at most {SWEEP2_MAX_ROWS} KKT rows (got {rows}); use PIVOT_STATIC or PIVOT_EIGEN")
 MODEL_ROBOT, MODEL_CSTR, MODEL_PARKING, MODEL_ROBOT_NG, MODEL_KITE_STANDIN, MODEL_PARKING_NG = 0, 1, 2, 3, 4, 5
 NLP_CONSTRAINED_ROSENBROCK, NLP_ROSENBROCK, NLP_SIMPLE, NLP_HS071 = 0, 1, 2, 3
+# the size-range problems of nlp_shapes.hpp (ORC_NLP_*), by the name they are registered under on the device
+NLP_SHAPES = {"ChainRosen9": 10, "Sphere12": 11, "Cuts8": 12, "Wave64": 13, "Wide60": 14, "Unc64": 15, "Param70": 16}
+# (nx, ne, ni, np) of every NLP the checker knows
+NLP_DIMS = {NLP_CONSTRAINED_ROSENBROCK: (2, 1, 0, 0), NLP_ROSENBROCK: (2, 0, 0, 0), NLP_SIMPLE: (2, 0, 1, 0), NLP_HS071: (4, 1, 1, 0),
+            10: (9, 0, 0, 0), 11: (12, 1, 0, 0), 12: (8, 0, 40, 0), 13: (32, 16, 16, 2), 14: (60, 4, 0, 0), 15: (64, 0, 0, 0), 16: (10, 2, 3, 70)}
 QP_SOLVED, QP_MAX_ITER_EXCEEDED, QP_UNSOLVED = 0, 1, 2
 SQP_SOLVED, SQP_MAX_ITER_EXCEEDED = 0, 1
 
@@ -373,14 +378,29 @@ def sqp_trace_qps(model, P, S, t0, tf, d, lbx, ubx, lbg=None, ubg=None, x_guess=
 
 
 def nlp_solve(problem, x0, lbx=None, ubx=None, lbg=None, ubg=None, sqp_settings=None, qp_settings=None,
-              pivot=PIVOT_EIGEN, lam0=None):
-    dims = {NLP_CONSTRAINED_ROSENBROCK: (2, 1, 0), NLP_ROSENBROCK: (2, 0, 0), NLP_SIMPLE: (2, 0, 1), NLP_HS071: (4, 1, 1)}
-    n, ne, ni = dims[problem]
+              pivot=PIVOT_EIGEN, lam0=None, p=None):
+    """p: the instance's static parameters (problems with np > 0)"""
+    n, ne, ni, np_ = NLP_DIMS[problem]
+    if np_ and (p is None or len(p) != np_):
+        raise ValueError(f"problem {problem} takes {np_} static parameters")
     ss = sqp_settings or sqp_default_settings(); qs = qp_settings or sqp_qp_default_settings()
     x = np.zeros(n); lam = np.zeros(ne + ni + n); info = SQPInfo()
-    lib().orc_nlp_solve(problem, _p(_f(x0)), _p(_f(lam0)), _p(_f(lbx)), _p(_f(ubx)), _p(_f(lbg)), _p(_f(ubg)),
-                        C.byref(ss), C.byref(qs), pivot, _p(x), _p(lam), C.byref(info))
+    pp = _f(p) if np_ else None
+    lib().orc_nlp_solve_p(problem, _p(pp), _p(_f(x0)), _p(_f(lam0)), _p(_f(lbx)), _p(_f(ubx)), _p(_f(lbg)), _p(_f(ubg)),
+                          C.byref(ss), C.byref(qs), pivot, _p(x), _p(lam), C.byref(info))
     return x, lam, info
+
+
+def nlp_linearise(problem, x, lam, p=None):
+    """GenericNLP::lagrangian_gradient_hessian at one point: dict(cost, c (m,), jac (m, nx), cost_grad, lag_grad (nx,), lag_hess (nx, nx))"""
+    n, ne, ni, np_ = NLP_DIMS[problem]
+    m = ne + ni
+    if np_ and (p is None or len(p) != np_):
+        raise ValueError(f"problem {problem} takes {np_} static parameters")
+    cost = np.zeros(1); c = np.zeros(max(m, 1)); jac = np.zeros(max(m, 1) * n); cg = np.zeros(n); lg = np.zeros(n); lh = np.zeros(n * n)
+    pp = _f(p) if np_ else None
+    lib().orc_nlp_linearise(problem, _p(pp), _p(_f(x)), _p(_f(lam)), _p(cost), _p(c), _p(jac), _p(cg), _p(lg), _p(lh))
+    return dict(cost=cost[0], c=c[:m], jac=jac[:m * n].reshape(n, m).T.copy(), cost_grad=cg, lag_grad=lg, lag_hess=lh.reshape(n, n).T.copy())
 
 
 # ------------------------------------------------------------------------------------------------------------------

@@ -4,10 +4,11 @@
 // (cost_gradient_impl, cost_gradient_hessian_impl, lagrangian_gradient_impl, lagrangian_gradient_hessian_impl,
 // lines ~480-690). Used only to transcribe the SQP known-answer tests of
 // /root/reference/tests/solvers/sqp/sqp_test_autodiff.cpp (they pin SQP + boxADMM + BFGS end to end).
-// Def concept: enum {NX, NE, NI}; cost<T>(x,c); eq<T>(x,ce); ineq<T>(x,ci).
+// Def concept: enum {NX, NE, NI}; cost<T>(x,c); eq<T>(x,ce); ineq<T>(x,ci). A Def with static parameters holds them itself (ShapeDef::p).
 #pragma once
 #include <vector>
 #include "ad.hpp"
+#include "nlp_shapes.hpp"
 
 namespace oracle {
 
@@ -53,14 +54,16 @@ struct GenericNLP {
     }
     void lagrangian_gradient_hessian(const double* x, const double*, const double* lam, double& lag, double* lag_grad,
                                      double* H, double* cost_grad, double* g, double* jac) const {
-        ad2 v[NXV]; seed2(x, v); ad2 c(0.0);
+        std::vector<ad2> vh(NXV);   // on the heap: NX nested duals of NX x NX partials are megabytes at NX = 60
+        ad2* v = vh.data(); seed2(x, v); ad2 c(0.0);
         def.template cost<ad2>(v, c);
         lag = c.v.v;
         for (int j = 0; j < NXV; ++j) cost_grad[j] = c.v.d[j];
         for (int i = 0; i < NXV; ++i) for (int r = 0; r < NXV; ++r) H[r + i * NXV] = c.d[i].d[r];
         linearise_constraints(x, g, jac);
         finish_lag_grad(lam, lag_grad, cost_grad, jac);
-        ad2 ce[NE > 0 ? NE : 1], ci[NI > 0 ? NI : 1];
+        std::vector<ad2> ceh(NE > 0 ? NE : 1), cih(NI > 0 ? NI : 1);
+        ad2 *ce = ceh.data(), *ci = cih.data();
         if (NE > 0) def.template eq<ad2>(v, ce);
         for (int q = 0; q < NE; ++q)  // hes.col(i) = d[i].d ; transposeInPlace ; H += lam(q)*hes
             for (int i = 0; i < NXV; ++i) for (int r = 0; r < NXV; ++r) H[i + r * NXV] += lam[q] * ce[q].d[i].d[r];
@@ -105,6 +108,27 @@ struct HS071Def {
         ce[0] = (x[0] * x[0] + x[1] * x[1] + x[2] * x[2] + x[3] * x[3]) - T(40.0);
     }
     template <class T> void ineq(const T* x, T* ci) const { ci[0] = x[0] * x[1] * x[2] * x[3]; }
+};
+
+// the size-range problems of nlp_shapes.hpp through pointer views; `p` = the instance's static parameters (Body::NP of them)
+template <class T>
+struct PtrView {
+    T* q;
+    T& operator()(int i) const { return q[i]; }
+};
+template <class Body>
+struct ShapeDef {
+    enum { NX = Body::NX, NE = Body::NE, NI = Body::NI, NP = Body::NP };
+    const double* p = nullptr;
+    template <class T> void cost(const T* x, T& c) const { Body::cost(PtrView<const T>{x}, PtrView<const double>{p}, c); }
+    template <class T> void eq(const T* x, T* ce) const {
+        PtrView<T> o{ce};
+        Body::template eq<T>(PtrView<const T>{x}, PtrView<const double>{p}, o);
+    }
+    template <class T> void ineq(const T* x, T* ci) const {
+        PtrView<T> o{ci};
+        Body::template ineq<T>(PtrView<const T>{x}, PtrView<const double>{p}, o);
+    }
 };
 
 }  // namespace oracle

@@ -352,11 +352,15 @@ static void sqp_trace_impl(int* nrec, int P, int S, double t0, double tf, const 
     *nrec = k;
 }
 
+template <class Def> static void set_params(Def&, const double*) {}
+template <class Body> static void set_params(ShapeDef<Body>& d, const double* p) { d.p = p; }
+
 template <class Def>
-static void nlp_impl(const double* x0, const double* lam0, const double* lbx, const double* ubx, const double* lbg,
+static void nlp_impl(const double* p, const double* x0, const double* lam0, const double* lbx, const double* ubx, const double* lbg,
                      const double* ubg, const orc_sqp_settings* ss, const orc_qp_settings* qs, int pivot, double* x,
                      double* lam, orc_sqp_info* info) {
     GenericNLP<Def> prob;
+    set_params(prob.def, p);
     SQP<GenericNLP<Def>> sqp(prob, 0);
     sqp.settings = to_sqp(ss); sqp.qp.settings = to_qp(qs); sqp.qp.pivot = (pivot_policy)pivot;
     const int n = sqp.n, m = sqp.m, mi = sqp.mi;
@@ -372,6 +376,35 @@ static void nlp_impl(const double* x0, const double* lam0, const double* lbx, co
     info->primal_norm = sqp.primal_norm; info->dual_norm = sqp.dual_norm; info->max_violation = sqp.max_violation;
     info->cost = sqp.cost_;
 }
+
+template <class Def>
+static void nlp_linearise_impl(const double* p, const double* x, const double* lam, double* cost, double* constr, double* jac,
+                               double* cost_grad, double* lag_grad, double* lag_hess) {
+    GenericNLP<Def> prob;
+    set_params(prob.def, p);
+    const int n = Def::NX, m = Def::NE + Def::NI;
+    std::vector<double> g(m > 0 ? m : 1), J(m > 0 ? m * n : 1);
+    prob.lagrangian_gradient_hessian(x, nullptr, lam, *cost, lag_grad, lag_hess, cost_grad, g.data(), J.data());
+    std::memcpy(constr, g.data(), sizeof(double) * m);
+    std::memcpy(jac, J.data(), sizeof(double) * m * n);
+}
+
+// every NLP the checker knows, by its ORC_NLP_* id
+#define DISPATCH_NLP(problem, fn, ...)                                                                  \
+    switch (problem) {                                                                                  \
+        case ORC_NLP_CONSTRAINED_ROSENBROCK: fn<ConstrainedRosenbrockDef>(__VA_ARGS__); break;          \
+        case ORC_NLP_ROSENBROCK: fn<RosenbrockDef>(__VA_ARGS__); break;                                 \
+        case ORC_NLP_SIMPLE: fn<SimpleNLPDef>(__VA_ARGS__); break;                                      \
+        case ORC_NLP_HS071: fn<HS071Def>(__VA_ARGS__); break;                                           \
+        case ORC_NLP_CHAIN_ROSEN9: fn<ShapeDef<nlp_shapes::ChainRosen9>>(__VA_ARGS__); break;           \
+        case ORC_NLP_SPHERE12: fn<ShapeDef<nlp_shapes::Sphere12>>(__VA_ARGS__); break;                  \
+        case ORC_NLP_CUTS8: fn<ShapeDef<nlp_shapes::Cuts8>>(__VA_ARGS__); break;                        \
+        case ORC_NLP_WAVE64: fn<ShapeDef<nlp_shapes::Wave64>>(__VA_ARGS__); break;                      \
+        case ORC_NLP_WIDE60: fn<ShapeDef<nlp_shapes::Wide60>>(__VA_ARGS__); break;                      \
+        case ORC_NLP_UNC64: fn<ShapeDef<nlp_shapes::Unc64>>(__VA_ARGS__); break;                        \
+        case ORC_NLP_PARAM70: fn<ShapeDef<nlp_shapes::Param70>>(__VA_ARGS__); break;                    \
+        default: break;                                                                                 \
+    }
 
 extern "C" {
 
@@ -420,13 +453,16 @@ int orc_sqp_trace_qps(int model, int P, int S, double t0, double tf, const doubl
 void orc_nlp_solve(int problem, const double* x0, const double* lam0, const double* lbx, const double* ubx,
                    const double* lbg, const double* ubg, const orc_sqp_settings* ss, const orc_qp_settings* qs,
                    int pivot, double* x, double* lam, orc_sqp_info* info) {
-    switch (problem) {
-        case ORC_NLP_CONSTRAINED_ROSENBROCK: nlp_impl<ConstrainedRosenbrockDef>(x0, lam0, lbx, ubx, lbg, ubg, ss, qs, pivot, x, lam, info); break;
-        case ORC_NLP_ROSENBROCK: nlp_impl<RosenbrockDef>(x0, lam0, lbx, ubx, lbg, ubg, ss, qs, pivot, x, lam, info); break;
-        case ORC_NLP_SIMPLE: nlp_impl<SimpleNLPDef>(x0, lam0, lbx, ubx, lbg, ubg, ss, qs, pivot, x, lam, info); break;
-        case ORC_NLP_HS071: nlp_impl<HS071Def>(x0, lam0, lbx, ubx, lbg, ubg, ss, qs, pivot, x, lam, info); break;
-        default: break;
-    }
+    orc_nlp_solve_p(problem, nullptr, x0, lam0, lbx, ubx, lbg, ubg, ss, qs, pivot, x, lam, info);
+}
+void orc_nlp_solve_p(int problem, const double* p, const double* x0, const double* lam0, const double* lbx, const double* ubx,
+                     const double* lbg, const double* ubg, const orc_sqp_settings* ss, const orc_qp_settings* qs,
+                     int pivot, double* x, double* lam, orc_sqp_info* info) {
+    DISPATCH_NLP(problem, nlp_impl, p, x0, lam0, lbx, ubx, lbg, ubg, ss, qs, pivot, x, lam, info);
+}
+void orc_nlp_linearise(int problem, const double* p, const double* x, const double* lam, double* cost, double* constr, double* jac,
+                       double* cost_grad, double* lag_grad, double* lag_hess) {
+    DISPATCH_NLP(problem, nlp_linearise_impl, p, x, lam, cost, constr, jac, cost_grad, lag_grad, lag_hess);
 }
 
 }  // extern "C"

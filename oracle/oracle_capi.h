@@ -48,6 +48,9 @@ typedef struct {
 
 enum { ORC_MODEL_ROBOT = 0, ORC_MODEL_CSTR = 1, ORC_MODEL_PARKING = 2, ORC_MODEL_ROBOT_NG = 3, ORC_MODEL_KITE_STANDIN = 4, ORC_MODEL_PARKING_NG = 5 };
 enum { ORC_NLP_CONSTRAINED_ROSENBROCK = 0, ORC_NLP_ROSENBROCK = 1, ORC_NLP_SIMPLE = 2, ORC_NLP_HS071 = 3 };
+/* the size-range problems of nlp_shapes.hpp */
+enum { ORC_NLP_CHAIN_ROSEN9 = 10, ORC_NLP_SPHERE12 = 11, ORC_NLP_CUTS8 = 12, ORC_NLP_WAVE64 = 13, ORC_NLP_WIDE60 = 14, ORC_NLP_UNC64 = 15,
+       ORC_NLP_PARAM70 = 16 };
 
 /* sin / cos / exp used by the model evaluations: 0 (default) = pmpc::detmath, the IEEE-only restatement the HIP kernels share
  * (GPU-vs-oracle comparisons are bit for bit); 1 = glibc, what the reference binary calls. Process-wide; returns the old value. */
@@ -129,6 +132,14 @@ int orc_sqp_trace_qps(int model, int P, int S, double t0, double tf, const doubl
 void orc_nlp_solve(int problem, const double* x0, const double* lam0, const double* lbx, const double* ubx,
                    const double* lbg, const double* ubg, const orc_sqp_settings* ss, const orc_qp_settings* qs,
                    int pivot, double* x, double* lam, orc_sqp_info* info);
+/* the same with the instance's static parameters p (nlp_shapes.hpp problems; null for a problem without any) */
+void orc_nlp_solve_p(int problem, const double* p, const double* x0, const double* lam0, const double* lbx, const double* ubx,
+                     const double* lbg, const double* ubg, const orc_sqp_settings* ss, const orc_qp_settings* qs,
+                     int pivot, double* x, double* lam, orc_sqp_info* info);
+/* GenericNLP::lagrangian_gradient_hessian at one point: cost, constraints [eq | ineq], Jacobian (m x nx column-major), cost gradient,
+   Lagrangian gradient, Lagrangian Hessian (nx x nx column-major) */
+void orc_nlp_linearise(int problem, const double* p, const double* x, const double* lam, double* cost, double* constr, double* jac,
+                       double* cost_grad, double* lag_grad, double* lag_hess);
 
 #ifdef __cplusplus
 }

@@ -192,11 +192,12 @@ struct NlpSqp {
         c = fmax(c, a); c = fmax(c, b);
         return c;
     }
-    // max |v_i| over count <= 64 entries, one per lane
+    // max |v_i| over count <= 64 entries, one per lane, from 0 as the checker's fmax fold (BoxADMM::inf_norm) starts: a NaN entry is
+    // skipped, and a vector of NaNs has norm 0. The 0 seed matters at count = 64, where no idle lane contributes a 0 to the reduction.
     __device__ double inf_norm(const double* v, int count) const {
         const int ln = lane_id();
         const double a = fabs(v[ln < count ? ln : 0]);
-        return wave_max(ln < count ? a : 0.0);
+        return fmax(0.0, wave_max(ln < count ? a : 0.0));
     }
 
     // ---- regularisation (sqp_test_autodiff.cpp:29-45, dense_sparse_compare.cpp:109-122) in the checker's form

@@ -59,10 +59,12 @@ def _same(a, b):
     return (a.view(np.int64) == b.view(np.int64)) | (np.isnan(a) & np.isnan(b))
 
 
-def _oracle_batch(oracle, problem, X0, so, lbx=None, ubx=None, lbg=None, ubg=None):
+def _oracle_batch(oracle, problem, X0, so, lbx=None, ubx=None, lbg=None, ubg=None, lam0=None, P=None, qo=None):
+    """the checker on every row; lam0 / P (static parameters) / qo (QP settings) are optional as in oracle.nlp_solve"""
     def one(i):
         return oracle.nlp_solve(problem, X0[i], lbx=None if lbx is None else lbx[i], ubx=None if ubx is None else ubx[i],
-                                lbg=None if lbg is None else lbg[i], ubg=None if ubg is None else ubg[i], sqp_settings=so, pivot=oracle.PIVOT_SWEEP)
+                                lbg=None if lbg is None else lbg[i], ubg=None if ubg is None else ubg[i], sqp_settings=so, pivot=oracle.PIVOT_SWEEP,
+                                lam0=None if lam0 is None else lam0[i], p=None if P is None else P[i], qp_settings=qo)
     with ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 1)) as ex:
         return list(ex.map(one, range(len(X0))))
 

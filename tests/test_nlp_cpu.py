@@ -13,6 +13,7 @@ import pytest
 HERE = os.path.dirname(os.path.abspath(__file__))
 CPP = os.path.join(HERE, "cpp")
 USER_SO = os.path.join(CPP, "libuser_nlp.so")
+SHAPES_SO = os.path.join(CPP, "libuser_nlp_shapes.so")
 MIRROR = os.path.join(CPP, "nlp_mirror_test")
 LLVM = "/opt/rocm/lib/llvm/bin"
 MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
@@ -69,15 +70,29 @@ def _code_objects(path, tmp):
     return out
 
 
+def test_shapes_library_dims_match_checker(built):
+    """the size-range problems of oracle/nlp_shapes.hpp, as registered on the device (tests/cpp/user_nlp_shapes.hip), have the dimensions
+    of the checker's table"""
+    from polympc_amd import capi
+    from oracle import binding
+    assert os.path.exists(SHAPES_SO)
+    for name, pid in binding.NLP_SHAPES.items():
+        d = capi.UserNLP(SHAPES_SO, name).dims
+        assert (d["nx"], d["ne"], d["ni"], d["np"]) == binding.NLP_DIMS[pid], name
+        assert d["nx"] + d["m"] <= 64, name
+    assert max(d["nx"] + d["m"] for d in (capi.UserNLP(SHAPES_SO, n).dims for n in binding.NLP_SHAPES)) == 64
+
+
 @pytest.mark.skipif(not (os.path.exists(f"{LLVM}/clang-offload-bundler") and os.path.exists(f"{LLVM}/llvm-objdump")), reason="ROCm binutils not installed")
-def test_user_nlp_library_has_no_unproven_exec_window_and_no_lane_losing_spill(built):
+@pytest.mark.parametrize("lib_name", ["libuser_nlp.so", "libuser_nlp_shapes.so"])
+def test_user_nlp_library_has_no_unproven_exec_window_and_no_lane_losing_spill(built, lib_name):
     """The checks tests/test_kernel_occupancy_cpu.py makes of the product library, made of a USER-compiled library: the register QP's one-lane
     EXEC windows (pivot_lane_setup) start at full EXEC in every kernel the user's hipcc built, and no accumulation-register or scratch spill is
-    read back with lanes its write did not cover."""
+    read back with lanes its write did not cover. libuser_nlp_shapes.so holds the problems of 9 to 64 variables (up to 64 KKT rows)."""
     sys.path.insert(0, HERE)
     import tools_exec_regions as ter
     with tempfile.TemporaryDirectory() as tmp:
-        objs = _code_objects(built, tmp)
+        objs = _code_objects(os.path.join(CPP, lib_name), tmp)
         assert objs
         kernels, bodies, bad, bad_agpr = 0, 0, [], []
         for co in objs:

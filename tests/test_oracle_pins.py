@@ -310,6 +310,46 @@ def test_regularisers(oracle):
     assert np.allclose(Hg, exp)
 
 
+@pytest.mark.parametrize("n", [9, 12, 33, 60, 64])
+def test_regularise_eig_mirror_round_robin_matches_eigh(oracle, n):
+    """above 8 variables the checker's Jacobi runs in round-robin order (odd n with a dummy pair): its mirrored matrix is numpy's"""
+    rng = np.random.default_rng(n)
+    A = rng.standard_normal((n, n))
+    H = 0.5 * (A + A.T)
+    w, V = np.linalg.eigh(H)
+    assert w.min() < 0 < w.max()
+    w2 = np.where(w <= 0, -w + 0.1, w)
+    assert np.allclose(oracle.regularise(1, H), V @ np.diag(w2) @ V.T, atol=1e-10)
+
+
+def test_nlp_shapes_checker_linearisation_and_known_answers(oracle):
+    """the checker's GenericNLP on the size-range problems of nlp_shapes.hpp: derivatives within 1e-12 of numpy's closed forms, and the
+    manufactured x* reached from nearby starts (tests/test_gpu_nlp_shapes.py holds the device to the checker bit for bit)"""
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import nlp_shapes_ref as R
+    rng = np.random.default_rng(3)
+    for name, sh in R.SHAPES.items():
+        pid = oracle.NLP_SHAPES[name]
+        assert oracle.NLP_DIMS[pid] == (sh.nx, sh.ne, sh.ni, sh.npar)
+        k = sh.kkt(rng)
+        x = k["xs"] + rng.uniform(-0.5, 0.5, sh.nx); lam = rng.uniform(-2, 2, sh.m + sh.nx)
+        o = oracle.nlp_linearise(pid, x, lam, p=k["p"])
+        f, g, H, c, J, Hc = sh.eval(x, k["p"])
+        want = dict(cost=f, c=c, jac=J, cost_grad=g, lag_grad=g + J.T @ lam[:sh.m] + lam[sh.m:],
+                    lag_hess=H + sum(lam[q] * Hq for q, Hq in enumerate(Hc)))
+        for key, v in want.items():
+            assert np.abs(o[key] - v).max(initial=0.0) <= 1e-12 * max(1.0, np.abs(v).max(initial=0.0)), (name, key)
+        assert max(R.kkt_residuals(sh, k["xs"], k["lam"], k["p"], k["lbx"], k["ubx"], k["lbg"], k["ubg"])) <= 1e-14
+        ss = oracle.sqp_default_settings(); ss.max_iter = 100; ss.line_search_max_iter = 5; ss.regularisation = 1; ss.exact_hessian_every_iter = 1
+        ss.eps_prim = ss.eps_dual = 1e-7
+        qs = oracle.sqp_qp_default_settings(); qs.eps_abs = qs.eps_rel = 1e-10; qs.max_iter = 4000
+        xo, lo, info = oracle.nlp_solve(pid, k["xs"] + rng.uniform(-0.1, 0.1, sh.nx), lbx=k["lbx"], ubx=k["ubx"], lbg=k["lbg"], ubg=k["ubg"],
+                                        sqp_settings=ss, qp_settings=qs, pivot=oracle.PIVOT_SWEEP, p=k["p"])
+        assert info.status == 0, (name, info.status)
+        assert np.abs(xo - k["xs"]).max() <= 1e-5, name
+        assert max(R.kkt_residuals(sh, xo, lo, k["p"], k["lbx"], k["ubx"], k["lbg"], k["ubg"])) <= 1e-4, name
+
+
 # ---------------------------------------------------------------- A14/A15: SQP end to end (sqp_test_autodiff.cpp)
 def _nlp_settings(oracle):
     ss = oracle.sqp_default_settings(); ss.max_iter = 50; ss.line_search_max_iter = 5; ss.regularisation = 1
