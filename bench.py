@@ -12,10 +12,12 @@ scaling, no data-path collective); torch.distributed (RCCL) is used only for the
 `python bench.py --gpus N` on its own starts the N ranks itself (torch.distributed.run on 127.0.0.1); launched by a
 driver through torch.distributed.run it finds WORLD_SIZE in the environment and must be told the same N.
 
-Beside the headline the JSON line carries (rank 0, N = 1 only): per-step min / median / max, `configs` (BASELINE.json
-configs[2..4]: CSTR 16 384, kite stand-in 1024, scenario 8192 per GPU — a few steps each), `qp_replay` (a flat batch
-of QPs with the collocation structure through the QP entry point alone), `cpu_baseline` (CPU restatement of the reference,
-single core and all usable cores) and two parity objects over the whole batch.
+A plain run sets up, warms up, times the steps, writes `--dump-outputs` if asked and prints the line: the headline, per-step
+min / median / max and the headline kernel's roofline, all from the timed steps. `--full` adds what takes runs of its own
+(rank 0, N = 1 only): the block-BFGS variant and small batches of the headline workload, `configs` (BASELINE.json configs[2..4]:
+CSTR 16 384, kite stand-in 1024, scenario 8192 per GPU — a few steps each), `qp_replay` (a flat batch of QPs with the
+collocation structure through the QP entry point alone), `cpu_baseline` (CPU restatement of the reference, single core and all
+usable cores) and the parity objects against that restatement.
 
 Output (round 5): the DETAILED record goes to a file (`--detail-out`, default gpurun_out/bench_detail.json) and to stderr on one line prefixed
 `DETAIL `; stdout carries exactly ONE line, printed last: the compact contract line built by `contract_line()` (< 4 KB — a CPU test pins the
@@ -206,11 +208,13 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true", help="after the headline, also run the sub-records (block-BFGS variant, small batches, "
+                    "--configs, QP replay) and the CPU leg (baseline and parity objects); rank 0, N = 1 only")
     ap.add_argument("--batch", type=int, default=4096, help="OCP instances per GPU")
-    ap.add_argument("--cpu-sample", type=int, default=4096, help="instances per pass of the CPU-baseline sample (0 = skip)")
-    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="minimum wall time of the all-core CPU-baseline sample (single core: half)")
-    ap.add_argument("--configs", default="B,C,D,R,P", help="sub-records beside the headline (N = 1 only): any of B, C, D (BASELINE.json configs[2..4]) R (the reference's own 16-node robot grid, 128 KKT rows) and P (the problems of the reference's two NP = 1 control tests as batches); '' = none")
-    ap.add_argument("--no-replay", action="store_true", help="skip the QP-only replay record")
+    ap.add_argument("--cpu-sample", type=int, default=4096, help="with --full: instances per pass of the CPU-baseline sample (0 = skip)")
+    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="with --full: minimum wall time of the all-core CPU-baseline sample (single core: half)")
+    ap.add_argument("--configs", default="B,C,D,R,P", help="with --full, sub-records beside the headline (N = 1 only): any of B, C, D (BASELINE.json configs[2..4]) R (the reference's own 16-node robot grid, 128 KKT rows) and P (the problems of the reference's two NP = 1 control tests as batches); '' = none")
+    ap.add_argument("--no-replay", action="store_true", help="with --full: skip the QP-only replay record")
     ap.add_argument("--min-seconds", type=float, default=0.0, help="0 (default): one timed block of exactly --steps steps. S > 0: repeat that block until S seconds of timed work "
                     "have run and report the median block")
     ap.add_argument("--max-blocks", type=int, default=400)
@@ -401,7 +405,7 @@ def main():
                                  "dependent-chain latency, not by HBM: see roofline_fp64 and DESIGN.md"},
             "roofline_fp64": {"bound": "fp64-valu", "achieved": ach_tf, "peak": PEAK_FP64_TFLOPS, "unit": "TFLOP/s", "frac": ach_tf / PEAK_FP64_TFLOPS},
         }
-        if world == 1:
+        if args.full and world == 1:
             # the same batch with the Hessian update the reference's own mobile-robot MPC test plugs in (mpc_wrapper_test.cpp:100-105:
             # ContinuousOCP's block BFGS). Reported beside the bench line, which stays on SQPBase's defaults (dense damped BFGS).
             v = sqp_record(wl, B, max(3, args.steps // 2), args.warmup, "sqp_kernel<RobotOCP,35,21,HU=1>", hessian_update=1)
@@ -502,7 +506,7 @@ def main():
                                     "solved_fraction": float((qinf["status"] == pa.QP_SOLVED).mean()),
                                     "roofline_hbm_frac": qp_algorithmic_bytes(n, m) * Bq / med / 1e9 / PEAK_HBM_GBS,
                                     "roofline_fp64_frac": qp_algorithmic_flops(n, m, itq, fq) * Bq / med / 1e12 / PEAK_FP64_TFLOPS}
-        if args.cpu_sample > 0 and world == 1:
+        if args.full and args.cpu_sample > 0 and world == 1:
             from oracle import binding as ob   # CPU restatement of the reference algorithm: baseline / checker only, never the product path
             Bc = min(args.cpu_sample, B)
             cores = usable_cpus()
