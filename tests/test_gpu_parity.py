@@ -96,13 +96,14 @@ def _policy_order(oracle, n, m, nodes, ruiz=False, block_bfgs=False, kkt_form=0,
     return _lds_order(oracle, n + m, ruiz=ruiz, kkt_form=kkt_form)
 
 
-def _qp_oracle(oracle, q, s, x0=None, y0=None):
+def _qp_oracle(oracle, q, s, x0=None, y0=None, pivot=None, threads=1):
+    """The restatement in the order of the kernel that serves this shape (pivot: another order, e.g. PIVOT_EIGEN for linear_solver = 1)."""
     os_ = oracle.qp_default_settings()
     for f, _ in s._fields_:
         setattr(os_, f, getattr(s, f))
     n, m = q["h"].shape[1], q["Alb"].shape[1]
     return oracle.qp_solve_batch(q["H"], q["h"], q["A"], q["Alb"], q["Aub"], q["xlb"], q["xub"], settings=os_,
-                                 pivot=_gpu_order(oracle, n, m), x0=x0, y0=y0)
+                                 pivot=_gpu_order(oracle, n, m) if pivot is None else pivot, x0=x0, y0=y0, threads=threads)
 
 
 
@@ -237,7 +238,7 @@ def test_qp_warm_start_guess(ctx, oracle):
     x, y, info = ctx.qp_solve_batch(q["H"], q["h"], q["A"], q["Alb"], q["Aub"], q["xlb"], q["xub"], settings=s, x0=x0, y0=y0)
     xo, yo, io = _qp_oracle(oracle, q, s, x0=x0, y0=y0)
     assert [int(i) for i in info["iter"]] == [i.iter for i in io]
-    assert np.abs(x - xo).max() <= 1e-9 and np.abs(y - yo).max() <= 1e-9
+    assert np.array_equal(x, xo) and np.array_equal(y, yo), (np.abs(x - xo).max(), np.abs(y - yo).max())   # bit for bit, like every other QP-entry test
 
 
 def test_qp_from_sqp_trace_vs_oracle(ctx, oracle):

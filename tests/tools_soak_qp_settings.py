@@ -15,10 +15,7 @@ import polympc_amd as pa                       # noqa: E402
 from polympc_amd import workloads              # noqa: E402
 from oracle import binding as ob               # noqa: E402
 import test_gpu_parity as T                    # noqa: E402
-
-VARIANTS = [dict(), dict(adaptive_rho=0), dict(check_termination=1), dict(check_termination=25, adaptive_rho_interval=7), dict(max_iter=7),
-            dict(rho=1.0), dict(alpha=1.6), dict(sigma=1e-3), dict(eps_abs=1e-6, eps_rel=1e-6), dict(adaptive_rho_tolerance=1.5, adaptive_rho_interval=10),
-            dict(check_termination=0, max_iter=40)]
+from qp_settings_variants import VARIANTS     # noqa: E402  (the list the QP-entry tests of tests/test_gpu_qp_settings.py run as well)
 
 
 def main():
