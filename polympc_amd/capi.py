@@ -80,7 +80,7 @@ BUILD_DIR = os.path.join(HERE, "_build")
 
 def build_library(force=False, verbose=False, jobs=None):
     """Cross-compile the HIP library for gfx950 in-tree (works without a GPU): one object per translation unit
-    (pmpc_api.hip + one pmpc_model_*.hip per built-in OCP), compiled in parallel, then linked."""
+    (every .hip under csrc/: pmpc_api.hip, pmpc_qp_entry.hip, one pmpc_model_*.hip per built-in OCP, ...), compiled in parallel, then linked."""
     from concurrent.futures import ThreadPoolExecutor
     files = sorted(os.listdir(CSRC))
     units = sorted((f for f in files if f.endswith(".hip")), key=lambda f: (not f.startswith("pmpc_model_"), not f.startswith("pmpc_grids_"), f))   # longest translation units first

@@ -1,4 +1,5 @@
-// polympc_amd — kernels + the C ABI declared in include/polympc_amd.h (gfx950 only, no CPU fallback).
+// polympc_amd — the C ABI declared in include/polympc_amd.h (gfx950 only, no CPU fallback): the context, the utilities, the SQP entry points, the
+// MPC façade and the sharded solve. The QP and Ruiz entry points, with their kernels and launch plan, are in pmpc_qp_entry.hip.
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
@@ -12,97 +13,10 @@
 #include "pmpc_context.hpp"
 #include "pmpc_builtin.hpp"
 #include "pmpc_ocp.hpp"
-#include "pmpc_qp.hpp"
-#include "pmpc_qp_reg.hpp"
 #include "pmpc_sqp.hpp"
 #include "pmpc_launch.hpp"
-#include "pmpc_ruiz.hpp"
-#include "pmpc_admm.hpp"
-
 
 using namespace pmpc;
-
-extern "C" int pmpc_internal_qp_reg2_launch(void* stream, int B, int n, int m, const double* H, const double* h, const double* A, const double* Alb,
-                                            const double* Aub, const double* xlb, const double* xub, const double* x0, const double* y0,
-                                            const pmpc_qp_settings* s, double* x, double* y, pmpc_qp_info* info);
-
-// =====================================================================================================================
-// kernels: one 64-lane workgroup (= one wavefront) per instance; grid = batch
-// =====================================================================================================================
-__device__ __forceinline__ void qp_boxadmm_one(int b, int n, int m, const double* __restrict__ H, const double* __restrict__ h, const double* __restrict__ A,
-                                               const double* __restrict__ Alb, const double* __restrict__ Aub, const double* __restrict__ xlb,
-                                               const double* __restrict__ xub, const double* __restrict__ x0, const double* __restrict__ y0,
-                                               const pmpc_qp_settings& s, double* __restrict__ x, double* __restrict__ y, pmpc_qp_info* __restrict__ info,
-                                               double* smem, int extra_flags) {
-    QpLds w;
-    double* p = w.carve(smem, n, m);
-    // stage the vectors the ADMM loop touches every iteration: h, Alb, Aub, xlb, xub
-    double* hL = p; p += n; double* albL = p; p += m; double* aubL = p; p += m; double* xlbL = p; p += n; double* xubL = p; p += n;
-    const int ln = lane_id();
-    for (int i = ln; i < n; i += WAVE) { hL[i] = h[(size_t)b * n + i]; xlbL[i] = xlb[(size_t)b * n + i]; xubL[i] = xub[(size_t)b * n + i]; }
-    for (int i = ln; i < m; i += WAVE) { albL[i] = Alb[(size_t)b * m + i]; aubL[i] = Aub[(size_t)b * m + i]; }
-    wsync();
-    pmpc_qp_info qi;
-    boxadmm_solve(w, n, m, H + (size_t)b * n * n, n, hL, A + (size_t)b * m * n, m, albL, aubL, xlbL, xubL,
-                  x0 ? x0 + (size_t)b * n : nullptr, y0 ? y0 + (size_t)b * (n + m) : nullptr, s, qi);
-    for (int i = ln; i < n; i += WAVE) x[(size_t)b * n + i] = w.x[i];
-    for (int i = ln; i < n + m; i += WAVE) y[(size_t)b * (n + m) + i] = w.y[i];
-    qi.flags |= extra_flags;
-    if (ln == 0) info[b] = qi;
-    wsync();
-}
-__global__ __launch_bounds__(64) void qp_boxadmm_kernel(int B, int n, int m, const double* __restrict__ H,
-                                                        const double* __restrict__ h, const double* __restrict__ A,
-                                                        const double* __restrict__ Alb, const double* __restrict__ Aub,
-                                                        const double* __restrict__ xlb, const double* __restrict__ xub,
-                                                        const double* __restrict__ x0, const double* __restrict__ y0,
-                                                        pmpc_qp_settings s, double* __restrict__ x, double* __restrict__ y,
-                                                        pmpc_qp_info* __restrict__ info, int redo) {
-    extern __shared__ double smem[];
-    if (redo) {
-        // redo launch behind a one-row-per-lane register kernel (grid = ceil(B / 64)): this workgroup looks at 64 QPs at once — one word each — and solves,
-        // one after the other, those that gave up at their conditioning gate (PMPC_FLAG_ILLCOND; normally none: 256 workgroups that read a word and exit
-        // behind 16 384 QPs instead of 16 384 of them — the QP entry point's batches are flat and large, and a workgroup launch is not free)
-        const int base = (int)blockIdx.x * WAVE, ln = lane_id();
-        const int fl = (base + ln < B) ? info[base + ln].flags : 0;
-        unsigned long long todo = __builtin_amdgcn_ballot_w64((fl & PMPC_FLAG_ILLCOND) != 0);
-        while (todo) {
-            const int i = __builtin_ctzll(todo);
-            todo &= todo - 1;
-            qp_boxadmm_one(base + i, n, m, H, h, A, Alb, Aub, xlb, xub, x0, y0, s, x, y, info, smem, PMPC_FLAG_ILLCOND);   // (the flag stays: this QP took the full KKT form)
-        }
-        return;
-    }
-    const int b = blockIdx.x;
-    if (b >= B) return;
-    qp_boxadmm_one(b, n, m, H, h, A, Alb, Aub, xlb, xub, x0, y0, s, x, y, info, smem, 0);
-}
-// register-resident specialisation for compile-time (NN, MM), NN+MM <= 64
-template <int NN, int MM>
-__global__ __launch_bounds__(64, 2) void qp_boxadmm_reg_kernel(int B, const double* __restrict__ H, const double* __restrict__ h,
-                                                            const double* __restrict__ A, const double* __restrict__ Alb,
-                                                            const double* __restrict__ Aub, const double* __restrict__ xlb,
-                                                            const double* __restrict__ xub, const double* __restrict__ x0,
-                                                            const double* __restrict__ y0, pmpc_qp_settings s,
-                                                            double* __restrict__ x, double* __restrict__ y, pmpc_qp_info* __restrict__ info) {
-    __shared__ double tr[RegKkt<NN + MM>::TRI];
-    const int b = blockIdx.x;
-    if (b >= B) return;
-    pmpc_qp_info qi;
-    boxadmm_solve_reg<NN, MM, false, true, true>(H + (size_t)b * NN * NN, h + (size_t)b * NN, A + (size_t)b * MM * NN, Alb + (size_t)b * MM, Aub + (size_t)b * MM,
-                              xlb + (size_t)b * NN, xub + (size_t)b * NN, x0 ? x0 + (size_t)b * NN : nullptr,
-                              y0 ? y0 + (size_t)b * (NN + MM) : nullptr, s, qi, x + (size_t)b * NN, y + (size_t)b * (NN + MM), tr);
-    if (lane_id() == 0) info[b] = qi;
-}
-static size_t qp_kernel_lds_bytes(int n, int m) { return (QpLds::doubles(n, m) + 3 * (size_t)n + 2 * (size_t)m) * sizeof(double); }
-
-extern "C" size_t pmpc_internal_qp_big_ws_doubles(int n, int m);
-extern "C" size_t pmpc_internal_qp_big_lds_bytes(int n, int m);
-extern "C" int pmpc_internal_qp_big_launch(void* stream, double* Kws, int B, int n, int m, const double* H, const double* h, const double* A,
-                                           const double* Alb, const double* Aub, const double* xlb, const double* xub, const double* x0,
-                                           const double* y0, const pmpc_qp_settings* s, double* x, double* y, pmpc_qp_info* info);
-constexpr int PMPC_QP_BIG_MIN_ROWS = 112;   // measured on 4096 random QPs, 51 iterations (HBM factor vs LDS triangle): 96 rows 4.8 vs 3.8 ms, 128 rows 6.8 vs 7.4, 168 rows 12.5 vs 73.1
-                                             // (the fused SQP kernel switches at 96: its LDS-resident variant carries the SQP vectors too, pmpc_launch.hpp)
 
 extern "C" pmpc_status pmpc_internal_services(pmpc_context* ctx, int P, int S, double t0, double tf, size_t ws_bytes, const void** cheb,
                                                double** ws, void** stream, size_t* lds_limit, unsigned long long** phase_cycles, int* force_lds) {
@@ -125,7 +39,6 @@ extern "C" int pmpc_internal_simd_count(pmpc_context* ctx) { return ctx ? ctx->s
 extern "C" int pmpc_internal_switch(pmpc_context* ctx, int which) { return ctx ? (int)((ctx->dev_switches >> which) & 1u) : 0; }
 extern "C" void pmpc_internal_set_route(pmpc_context* ctx, int route) { if (ctx) ctx->last_route = route; }
 extern "C" int pmpc_internal_last_route(pmpc_context* ctx) { return ctx ? ctx->last_route : 0; }
-
 
 // =====================================================================================================================
 // C ABI
@@ -316,185 +229,6 @@ pmpc_status pmpc_chebyshev(int P, double* nodes, double* weights, double* D) {
     return PMPC_OK;
 }
 
-pmpc_status pmpc_qp_boxadmm_solve_batch_dev(pmpc_context* ctx, int B, int n, int m, const double* H, const double* h,
-                                            const double* A, const double* Alb, const double* Aub, const double* xlb,
-                                            const double* xub, const double* x0, const double* y0,
-                                            const pmpc_qp_settings* settings, double* x, double* y, pmpc_qp_info* info) {
-    if (!ctx || B < 0 || n < 1 || m < 0 || !H || !h || !xlb || !xub || !settings || !x || !y || !info) return PMPC_ERR_INVALID_ARGUMENT;
-    if (m > 0 && (!A || !Alb || !Aub)) return PMPC_ERR_INVALID_ARGUMENT;
-    if ((x0 == nullptr) != (y0 == nullptr)) return PMPC_ERR_INVALID_ARGUMENT;
-    if (B == 0) return PMPC_OK;
-    HIPCHK(hipSetDevice(ctx->device));
-    if (settings->linear_solver != 0 && settings->linear_solver != 1) return PMPC_ERR_INVALID_ARGUMENT;
-    PMPC_POISON_DEVICE(ctx);
-    const bool static_order = settings->linear_solver == 0 && !ctx->force_lds_path;   // the register-resident specialisations factorise in a static order
-    // register-resident specialisations (one KKT row per lane): config A's QP and the QPs of the robot / CSTR grids of 4 to 8 nodes
-#define PMPC_REG1_CASE(NN_, MM_)                                                                                                             \
-    if (n == NN_ && m == MM_ && static_order) {                                                                                              \
-        hipLaunchKernelGGL((qp_boxadmm_reg_kernel<NN_, MM_>), dim3(B), dim3(WAVE), 0, ctx->stream, B, H, h, A, Alb, Aub, xlb, xub, x0, y0,   \
-                           *settings, x, y, info);                                                                                           \
-        /* redo launch: the QPs that gave up at the conditioning gate of the constraint-first sweep, on the LDS-resident static LDL^T */          \
-        const size_t ldsg_ = qp_kernel_lds_bytes(n, m);                                                                                      \
-        if (ldsg_ <= ctx->lds_limit && !pmpc_internal_switch(ctx, PMPC_SW_NO_REDO_LAUNCH)) {                                                                 \
-            HIPCHK(hipFuncSetAttribute((const void*)qp_boxadmm_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsg_));             \
-            hipLaunchKernelGGL(qp_boxadmm_kernel, dim3((B + WAVE - 1) / WAVE), dim3(WAVE), ldsg_, ctx->stream, B, n, m, H, h, A, Alb, Aub, xlb, xub, x0, y0, \
-                               *settings, x, y, info, 1);                                                                                    \
-        }                                                                                                                                    \
-        HIPCHK(hipGetLastError());                                                                                                           \
-        return PMPC_OK;                                                                                                                      \
-    }
-    PMPC_REG1_CASE(35, 21)
-    PMPC_REG1_CASE(20, 12)
-    PMPC_REG1_CASE(25, 15)
-    PMPC_REG1_CASE(30, 18)
-    PMPC_REG1_CASE(40, 24)
-    PMPC_REG1_CASE(24, 16)
-    PMPC_REG1_CASE(30, 20)
-    PMPC_REG1_CASE(36, 24)
-#undef PMPC_REG1_CASE
-    if (static_order) {   // 65..112 KKT rows with a two-rows-per-lane register specialisation (pmpc_qp_reg2.hip)
-        const int r2 = pmpc_internal_qp_reg2_launch((void*)ctx->stream, B, n, m, H, h, A, Alb, Aub, xlb, xub, x0, y0, settings, x, y, info);
-        if (r2 < 0) return PMPC_ERR_HIP;
-        if (r2 > 0) return PMPC_OK;
-    }
-    const size_t lds = qp_kernel_lds_bytes(n, m);
-    // From BIG_KKT_MIN_ROWS rows on (and whenever the packed triangle does not fit LDS: the reference's kite size, 464 rows) the factor lives in HBM as
-    // tiles (pmpc_qp_big.hip: blocked LDL^T with MFMA updates, one QP per SIMD instead of one or two per CU). The pivoted factorisation exists in LDS only.
-    if (static_order && n + m >= 16 && (lds > ctx->lds_limit || n + m >= PMPC_QP_BIG_MIN_ROWS)) {
-        if (pmpc_internal_qp_big_lds_bytes(n, m) > ctx->lds_limit) return PMPC_ERR_UNSUPPORTED_SIZE;
-        const pmpc_status ws = ensure_ws(ctx, (size_t)B * pmpc_internal_qp_big_ws_doubles(n, m) * sizeof(double));
-        if (ws != PMPC_OK) return ws;
-        if (pmpc_internal_qp_big_launch((void*)ctx->stream, ctx->ws, B, n, m, H, h, A, Alb, Aub, xlb, xub, x0, y0, settings, x, y, info) != 0) return PMPC_ERR_HIP;
-        return PMPC_OK;
-    }
-    if (lds > ctx->lds_limit) return PMPC_ERR_UNSUPPORTED_SIZE;
-    HIPCHK(hipFuncSetAttribute((const void*)qp_boxadmm_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(qp_boxadmm_kernel, dim3(B), dim3(WAVE), lds, ctx->stream, B, n, m, H, h, A, Alb, Aub, xlb, xub, x0, y0,
-                       *settings, x, y, info, 0);
-    HIPCHK(hipGetLastError());
-    return PMPC_OK;
-}
-
-
-pmpc_status pmpc_qp_boxadmm_solve_batch(pmpc_context* ctx, int B, int n, int m, const double* H, const double* h,
-                                        const double* A, const double* Alb, const double* Aub, const double* xlb,
-                                        const double* xub, const double* x0, const double* y0,
-                                        const pmpc_qp_settings* settings, double* x, double* y, pmpc_qp_info* info) {
-    if (!ctx || B < 0 || n < 1 || m < 0 || !H || !h || !xlb || !xub || !settings || !x || !y || !info) return PMPC_ERR_INVALID_ARGUMENT;
-    if (B == 0) return PMPC_OK;
-    HIPCHK(hipSetDevice(ctx->device));
-    double *dH, *dh, *dA, *dAlb, *dAub, *dxlb, *dxub, *dx0, *dy0, *dx, *dy; pmpc_qp_info* dinfo;
-    const size_t Bn = (size_t)B * n, Bm = (size_t)B * m;
-    H2D(0, H, Bn * n, dH); H2D(1, h, Bn, dh); H2D(2, (m ? A : nullptr), Bm * n, dA); H2D(3, (m ? Alb : nullptr), Bm, dAlb);
-    H2D(4, (m ? Aub : nullptr), Bm, dAub); H2D(5, xlb, Bn, dxlb); H2D(6, xub, Bn, dxub); H2D(7, x0, Bn, dx0); H2D(8, y0, Bn + Bm, dy0);
-    DEVOUT(9, Bn * sizeof(double), dx); DEVOUT(10, (Bn + Bm) * sizeof(double), dy); DEVOUT(11, (size_t)B * sizeof(pmpc_qp_info), dinfo);
-    if (m == 0) { DEVOUT(2, 8, dA); DEVOUT(3, 8, dAlb); DEVOUT(4, 8, dAub); }
-    pmpc_status st = pmpc_qp_boxadmm_solve_batch_dev(ctx, B, n, m, dH, dh, dA, dAlb, dAub, dxlb, dxub, dx0, dy0, settings, dx, dy, dinfo);
-    if (st != PMPC_OK) return st;
-    HIPCHK(hipMemcpyAsync(x, dx, Bn * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipMemcpyAsync(y, dy, (Bn + Bm) * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipMemcpyAsync(info, dinfo, (size_t)B * sizeof(pmpc_qp_info), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    return PMPC_OK;
-}
-
-pmpc_status pmpc_qp_admm_solve_batch_dev(pmpc_context* ctx, int B, int n, int m, const double* H, const double* h, const double* A,
-                                         const double* Alb, const double* Aub, const double* xlb, const double* xub, const double* x0,
-                                         const double* y0, const pmpc_qp_settings* settings, double* x, double* y, pmpc_qp_info* info) {
-    if (!ctx || B < 0 || n < 1 || m < 0 || !H || !h || !xlb || !xub || !settings || !x || !y || !info) return PMPC_ERR_INVALID_ARGUMENT;
-    if (m > 0 && (!A || !Alb || !Aub)) return PMPC_ERR_INVALID_ARGUMENT;
-    if ((x0 == nullptr) != (y0 == nullptr)) return PMPC_ERR_INVALID_ARGUMENT;
-    if (B == 0) return PMPC_OK;
-    HIPCHK(hipSetDevice(ctx->device));
-    const size_t lds = QpLds::doubles(n, m + n) * sizeof(double);   // the (2n+m)-row KKT factor + vectors of the stacked system
-    if (lds > ctx->lds_limit) return PMPC_ERR_UNSUPPORTED_SIZE;
-    HIPCHK(hipFuncSetAttribute((const void*)qp_admm_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    PMPC_POISON_DEVICE(ctx);
-    hipLaunchKernelGGL(qp_admm_kernel, dim3(B), dim3(WAVE), lds, ctx->stream, B, n, m, H, h, A, Alb, Aub, xlb, xub, x0, y0, *settings, x, y, info);
-    HIPCHK(hipGetLastError());
-    return PMPC_OK;
-}
-pmpc_status pmpc_qp_admm_solve_batch(pmpc_context* ctx, int B, int n, int m, const double* H, const double* h, const double* A,
-                                     const double* Alb, const double* Aub, const double* xlb, const double* xub, const double* x0,
-                                     const double* y0, const pmpc_qp_settings* settings, double* x, double* y, pmpc_qp_info* info) {
-    if (!ctx || B < 0 || n < 1 || m < 0 || !H || !h || !xlb || !xub || !settings || !x || !y || !info) return PMPC_ERR_INVALID_ARGUMENT;
-    if (B == 0) return PMPC_OK;
-    HIPCHK(hipSetDevice(ctx->device));
-    double *dH, *dh, *dA, *dAlb, *dAub, *dxlb, *dxub, *dx0, *dy0, *dx, *dy; pmpc_qp_info* dinfo;
-    const size_t Bn = (size_t)B * n, Bm = (size_t)B * m;
-    H2D(0, H, Bn * n, dH); H2D(1, h, Bn, dh); H2D(2, (m ? A : nullptr), Bm * n, dA); H2D(3, (m ? Alb : nullptr), Bm, dAlb);
-    H2D(4, (m ? Aub : nullptr), Bm, dAub); H2D(5, xlb, Bn, dxlb); H2D(6, xub, Bn, dxub); H2D(7, x0, Bn, dx0); H2D(8, y0, Bn + Bm, dy0);
-    DEVOUT(9, Bn * sizeof(double), dx); DEVOUT(10, (Bn + Bm) * sizeof(double), dy); DEVOUT(11, (size_t)B * sizeof(pmpc_qp_info), dinfo);
-    if (m == 0) { DEVOUT(2, 8, dA); DEVOUT(3, 8, dAlb); DEVOUT(4, 8, dAub); }
-    pmpc_status st = pmpc_qp_admm_solve_batch_dev(ctx, B, n, m, dH, dh, dA, dAlb, dAub, dxlb, dxub, dx0, dy0, settings, dx, dy, dinfo);
-    if (st != PMPC_OK) return st;
-    HIPCHK(hipMemcpyAsync(x, dx, Bn * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipMemcpyAsync(y, dy, (Bn + Bm) * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipMemcpyAsync(info, dinfo, (size_t)B * sizeof(pmpc_qp_info), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    return PMPC_OK;
-}
-
-pmpc_status pmpc_qp_ruiz_compute_batch_dev(pmpc_context* ctx, int B, int n, int m, double* H, double* h, double* A, double* Alb,
-                                           double* Aub, double* xlb, double* xub, double* D, double* E, double* c) {
-    if (!ctx || B < 0 || n < 1 || m < 0 || !H || !h || !xlb || !xub || !D || !c) return PMPC_ERR_INVALID_ARGUMENT;
-    if (m > 0 && (!A || !Alb || !Aub || !E)) return PMPC_ERR_INVALID_ARGUMENT;
-    if (B == 0) return PMPC_OK;
-    HIPCHK(hipSetDevice(ctx->device));
-    double* scratch = nullptr;
-    DEVOUT(23, (size_t)B * (n + m) * sizeof(double), scratch);
-    PMPC_POISON_DEVICE(ctx);
-    hipLaunchKernelGGL(ruiz_compute_kernel, dim3(B), dim3(WAVE), 0, ctx->stream, B, n, m, H, h, A, Alb, Aub, xlb, xub, D, E, c, scratch);
-    HIPCHK(hipGetLastError());
-    return PMPC_OK;
-}
-pmpc_status pmpc_qp_ruiz_unscale_batch_dev(pmpc_context* ctx, int B, int n, int m, const double* D, const double* E, const double* c,
-                                           double* x, double* y) {
-    if (!ctx || B < 0 || n < 1 || m < 0 || !D || !c || !x || !y || (m > 0 && !E)) return PMPC_ERR_INVALID_ARGUMENT;
-    if (B == 0) return PMPC_OK;
-    HIPCHK(hipSetDevice(ctx->device));
-    PMPC_POISON_DEVICE(ctx);
-    hipLaunchKernelGGL(ruiz_unscale_solution_kernel, dim3(B), dim3(WAVE), 0, ctx->stream, B, n, m, D, E, c, x, y);
-    HIPCHK(hipGetLastError());
-    return PMPC_OK;
-}
-pmpc_status pmpc_qp_ruiz_compute_batch(pmpc_context* ctx, int B, int n, int m, double* H, double* h, double* A, double* Alb,
-                                       double* Aub, double* xlb, double* xub, double* D, double* E, double* c) {
-    if (!ctx || B < 0 || n < 1 || m < 0 || !H || !h || !xlb || !xub || !D || !c) return PMPC_ERR_INVALID_ARGUMENT;
-    if (m > 0 && (!A || !Alb || !Aub || !E)) return PMPC_ERR_INVALID_ARGUMENT;
-    if (B == 0) return PMPC_OK;
-    HIPCHK(hipSetDevice(ctx->device));
-    double *dH, *dh, *dA, *dAlb, *dAub, *dxlb, *dxub, *dD, *dE, *dc;
-    const size_t Bn = (size_t)B * n, Bm = (size_t)B * m;
-    H2D(0, H, Bn * n, dH); H2D(1, h, Bn, dh); H2D(2, (m ? A : nullptr), Bm * n, dA); H2D(3, (m ? Alb : nullptr), Bm, dAlb);
-    H2D(4, (m ? Aub : nullptr), Bm, dAub); H2D(5, xlb, Bn, dxlb); H2D(6, xub, Bn, dxub);
-    DEVOUT(7, Bn * sizeof(double), dD); DEVOUT(8, (Bm + 1) * sizeof(double), dE); DEVOUT(9, (size_t)B * sizeof(double), dc);
-    if (m == 0) { DEVOUT(2, 8, dA); DEVOUT(3, 8, dAlb); DEVOUT(4, 8, dAub); }
-    pmpc_status st = pmpc_qp_ruiz_compute_batch_dev(ctx, B, n, m, dH, dh, dA, dAlb, dAub, dxlb, dxub, dD, dE, dc);
-    if (st != PMPC_OK) return st;
-#define D2H_(host, dev, count) HIPCHK(hipMemcpyAsync(host, dev, (size_t)(count) * sizeof(double), hipMemcpyDeviceToHost, ctx->stream))
-    D2H_(H, dH, Bn * n); D2H_(h, dh, Bn); D2H_(xlb, dxlb, Bn); D2H_(xub, dxub, Bn); D2H_(D, dD, Bn); D2H_(c, dc, B);
-    if (m > 0) { D2H_(A, dA, Bm * n); D2H_(Alb, dAlb, Bm); D2H_(Aub, dAub, Bm); D2H_(E, dE, Bm); }
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    return PMPC_OK;
-}
-pmpc_status pmpc_qp_ruiz_unscale_batch(pmpc_context* ctx, int B, int n, int m, const double* D, const double* E, const double* c,
-                                       double* x, double* y) {
-    if (!ctx || B < 0 || n < 1 || m < 0 || !D || !c || !x || !y || (m > 0 && !E)) return PMPC_ERR_INVALID_ARGUMENT;
-    if (B == 0) return PMPC_OK;
-    HIPCHK(hipSetDevice(ctx->device));
-    double *dD, *dE, *dc, *dx, *dy;
-    const size_t Bn = (size_t)B * n, Bm = (size_t)B * m;
-    H2D(0, D, Bn, dD); H2D(1, (m ? E : nullptr), Bm, dE); H2D(2, c, B, dc); H2D(3, x, Bn, dx); H2D(4, y, Bn + Bm, dy);
-    if (m == 0) DEVOUT(1, 8, dE);
-    pmpc_status st = pmpc_qp_ruiz_unscale_batch_dev(ctx, B, n, m, dD, dE, dc, dx, dy);
-    if (st != PMPC_OK) return st;
-    D2H_(x, dx, Bn); D2H_(y, dy, Bn + Bm);
-#undef D2H_
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    return PMPC_OK;
-}
-
 #define DISPATCH_MODEL(model, F, ...)                                            \
     switch (model) {                                                             \
         case PMPC_MODEL_ROBOT: return F<RobotOCP>(__VA_ARGS__);                  \
@@ -534,16 +268,23 @@ pmpc_status pmpc_ocp_linearise_batch(pmpc_context* ctx, int model, int P, int S,
     DISPATCH_MODEL(model, linearise_impl, ctx, P, S, t0, tf, mparams, n_mparams, B, var, d, lam, cost, constr, jac, cost_grad, lag_grad, lag_hess);
 }
 
-/* arguments every SQP entry point shares: the static parameters `d` are mandatory for models that have them (ND > 0), and at least one
- * SQP iteration must be allowed (max_iter <= 0 would launch nothing and leave the outputs unwritten) */
-static pmpc_status check_sqp_args(int model, int P, int S, const double* d, const pmpc_sqp_settings* ss) {
+/* The argument check of pmpc_sqp_solve_batch and its _dev twin, run before the first device call; callers return PMPC_OK for B == 0. The static
+ * parameters `d` are mandatory for models that have them (ND > 0), and at least one SQP iteration must be allowed (max_iter <= 0 would launch
+ * nothing and leave the outputs unwritten). The host wrapper has always answered an empty batch first, and regularisation after the model, the
+ * grid and `d`; the _dev twin answers regularisation ahead of them. */
+static pmpc_status check_sqp_args(bool host, pmpc_context* ctx, int model, int P, int S, int B, const double* d, const double* lbx, const double* ubx,
+                                  const pmpc_sqp_settings* ss, const pmpc_qp_settings* qs, double* x, double* lam, pmpc_sqp_info* info,
+                                  int* nd_out = nullptr, int* n = nullptr, int* me = nullptr, int* mi = nullptr) {
+    if (!ctx || B < 0 || !lbx || !ubx || !ss || !qs || !x || !lam || !info) return PMPC_ERR_INVALID_ARGUMENT;
+    if (host && B == 0) return PMPC_OK;
+    const bool reg_ok = ss->regularisation >= 0 && ss->regularisation <= 2;
+    if (!host && !reg_ok) return PMPC_ERR_INVALID_ARGUMENT;
     int nd = 0;
-    const pmpc_status st = pmpc_ocp_dims(model, P, S, nullptr, nullptr, nullptr, &nd, nullptr, nullptr, nullptr, nullptr);
+    const pmpc_status st = pmpc_ocp_dims(model, P, S, nullptr, nullptr, nullptr, &nd, nullptr, n, me, mi);
     if (st != PMPC_OK) return st;
-    if (nd > 0 && !d) return PMPC_ERR_INVALID_ARGUMENT;
-    if (ss && ss->max_iter < 1) return PMPC_ERR_INVALID_ARGUMENT;
-    if (ss && ss->iteration_trace && ss->iteration_trace_capacity < 1) return PMPC_ERR_INVALID_ARGUMENT;
-    if (ss && (ss->kkt_form < 0 || ss->kkt_form > 2)) return PMPC_ERR_INVALID_ARGUMENT;
+    if (nd_out) *nd_out = nd;
+    if ((nd > 0 && !d) || !reg_ok || ss->max_iter < 1 || (ss->iteration_trace && ss->iteration_trace_capacity < 1) || ss->kkt_form < 0 || ss->kkt_form > 2)
+        return PMPC_ERR_INVALID_ARGUMENT;
     return PMPC_OK;
 }
 
@@ -552,10 +293,8 @@ pmpc_status pmpc_sqp_solve_batch_dev(pmpc_context* ctx, int model, int P, int S,
                                      const double* lbx, const double* ubx, const double* lbg, const double* ubg,
                                      const pmpc_sqp_settings* ss, const pmpc_qp_settings* qs, double* x, double* lam,
                                      pmpc_sqp_info* info) {
-    if (!ctx || B < 0 || !lbx || !ubx || !ss || !qs || !x || !lam || !info) return PMPC_ERR_INVALID_ARGUMENT;
-    if (ss->regularisation < 0 || ss->regularisation > 2) return PMPC_ERR_INVALID_ARGUMENT;
-    { const pmpc_status ca = check_sqp_args(model, P, S, d, ss); if (ca != PMPC_OK) return ca; }
-    if (B == 0) return PMPC_OK;
+    const pmpc_status chk = check_sqp_args(false, ctx, model, P, S, B, d, lbx, ubx, ss, qs, x, lam, info);
+    if (chk != PMPC_OK || B == 0) return chk;
     HIPCHK(hipSetDevice(ctx->device));
     DISPATCH_MODEL(model, sqp_builtin_dev, ctx, P, S, t0, tf, mparams, n_mparams, B, x_guess, lam_guess, d, lbx, ubx, lbg, ubg, ss, qs, x, lam, info);
 }
@@ -590,8 +329,9 @@ pmpc_status pmpc_mpc_step_batch_dev(pmpc_context* ctx, int model, int P, int S, 
     hipLaunchKernelGGL(mpc_pin_initial_state_kernel, dim3((B * nx + 255) / 256), dim3(256), 0, ctx->stream, B, n, varx, nx, x0, lbx, ubx);
     // warm start: the previous solution is the guess (SQPBase::solve() starts from m_x / m_lam, sqp_base.hpp:569-581); the
     // kernel's guess and result pointers must not alias, so the guess is a device-to-device copy
-    double *xg, *lg;
-    DEVOUT(12, (size_t)B * n * sizeof(double), xg); DEVOUT(13, (size_t)B * (m + n) * sizeof(double), lg);
+    Staging stg(ctx);
+    double *xg = stg.out<double>(SLOT_SQP_XG, (size_t)B * n), *lg = stg.out<double>(SLOT_SQP_LG, (size_t)B * (m + n));
+    if (!stg.ok()) return stg.status;
     HIPCHK(hipMemcpyAsync(xg, x, (size_t)B * n * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
     HIPCHK(hipMemcpyAsync(lg, lam, (size_t)B * (m + n) * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
     st = pmpc_sqp_solve_batch_dev(ctx, model, P, S, t0, tf, mparams, n_mparams, B, xg, lg, d, lbx, ubx, lbg, ubg, ss, qs, x, lam, info);
@@ -668,30 +408,13 @@ pmpc_status pmpc_sqp_solve_batch(pmpc_context* ctx, int model, int P, int S, dou
                                  int n_mparams, int B, const double* x_guess, const double* lam_guess, const double* d,
                                  const double* lbx, const double* ubx, const double* lbg, const double* ubg,
                                  const pmpc_sqp_settings* ss, const pmpc_qp_settings* qs, double* x, double* lam, pmpc_sqp_info* info) {
-    if (!ctx || B < 0 || !lbx || !ubx || !ss || !qs || !x || !lam || !info) return PMPC_ERR_INVALID_ARGUMENT;
-    if (B == 0) return PMPC_OK;
-    int nx, nu, np, nd, ng, n, me, mi;
-    pmpc_status st = pmpc_ocp_dims(model, P, S, &nx, &nu, &np, &nd, &ng, &n, &me, &mi);
-    if (st != PMPC_OK) return st;
-    if (nd > 0 && !d) return PMPC_ERR_INVALID_ARGUMENT;
-    HIPCHK(hipSetDevice(ctx->device));
-    const int m = me + mi;
-    double *dxg, *dlg, *dd, *dlbx, *dubx, *dlbg, *dubg, *dx, *dlam; pmpc_sqp_info* dinfo;
-    H2D(12, x_guess, (size_t)B * n, dxg); H2D(13, lam_guess, (size_t)B * (m + n), dlg); H2D(14, (nd ? d : nullptr), (size_t)B * nd, dd);
-    if (!nd) DEVOUT(14, 8, dd);
-    H2D(15, lbx, (size_t)B * n, dlbx); H2D(16, ubx, (size_t)B * n, dubx);
-    H2D(17, (mi ? lbg : nullptr), (size_t)B * mi, dlbg); H2D(18, (mi ? ubg : nullptr), (size_t)B * mi, dubg);
-    DEVOUT(19, (size_t)B * n * sizeof(double), dx); DEVOUT(20, (size_t)B * (m + n) * sizeof(double), dlam);
-    DEVOUT(21, (size_t)B * sizeof(pmpc_sqp_info), dinfo);
-    st = pmpc_sqp_solve_batch_dev(ctx, model, P, S, t0, tf, mparams, n_mparams, B, dxg, dlg, dd, dlbx, dubx, dlbg, dubg, ss, qs, dx, dlam, dinfo);
-    if (st != PMPC_OK) return st;
-    HIPCHK(hipMemcpyAsync(x, dx, (size_t)B * n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipMemcpyAsync(lam, dlam, (size_t)B * (m + n) * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipMemcpyAsync(info, dinfo, (size_t)B * sizeof(pmpc_sqp_info), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    return PMPC_OK;
+    int nd, n, me, mi;
+    const pmpc_status chk = check_sqp_args(true, ctx, model, P, S, B, d, lbx, ubx, ss, qs, x, lam, info, &nd, &n, &me, &mi);
+    if (chk != PMPC_OK || B == 0) return chk;
+    return sqp_solve_host(ctx, B, n, me + mi, nd, mi, {x_guess, lam_guess, d, lbx, ubx, lbg, ubg, x, lam, info}, [&](const SqpBuffers& v) {
+        return pmpc_sqp_solve_batch_dev(ctx, model, P, S, t0, tf, mparams, n_mparams, B, v.x_guess, v.lam_guess, v.d, v.lbx, v.ubx, v.lbg, v.ubg, ss, qs, v.x, v.lam, v.info);
+    });
 }
-
 
 /* contiguous shards over n_ctx contexts, one PERSISTENT host thread per context (started on the context's first sharded call, joined
    by pmpc_destroy), no collective. The contexts must be distinct objects (two contexts on one device are fine; one context twice is not: its
@@ -743,7 +466,7 @@ pmpc_status pmpc_sqp_solve_batch_multi(pmpc_context* const* ctxs, int n_ctx, int
     return PMPC_OK;
 }
 
-/* Host-buffer wrapper around a user-registered OCP's device entry (PMPC_REGISTER_OCP): stage in, launch, stage out. */
+/* Host-buffer wrapper around a user-registered OCP's device entry (PMPC_REGISTER_OCP). */
 pmpc_status pmpc_sqp_solve_batch_user(pmpc_context* ctx, pmpc_sqp_dev_fn fn, const void* model, int nx, int nu, int np, int nd, int ng,
                                       int P, int S, double t0, double tf, int B, const double* x_guess, const double* lam_guess,
                                       const double* d, const double* lbx, const double* ubx, const double* lbg, const double* ubg,
@@ -751,22 +474,10 @@ pmpc_status pmpc_sqp_solve_batch_user(pmpc_context* ctx, pmpc_sqp_dev_fn fn, con
     if (!ctx || !fn || !model || B < 0 || !lbx || !ubx || !ss || !qs || !x || !lam || !info) return PMPC_ERR_INVALID_ARGUMENT;
     if (B == 0) return PMPC_OK;
     if (nd > 0 && !d) return PMPC_ERR_INVALID_ARGUMENT;
-    HIPCHK(hipSetDevice(ctx->device));
-    const int nn = P * S + 1, n = (nx + nu) * nn + np, me = nx * nn, mi = ng * nn, m = me + mi;
-    double *dxg, *dlg, *dd, *dlbx, *dubx, *dlbg, *dubg, *dx, *dlam; pmpc_sqp_info* dinfo;
-    H2D(12, x_guess, (size_t)B * n, dxg); H2D(13, lam_guess, (size_t)B * (m + n), dlg); H2D(14, (nd ? d : nullptr), (size_t)B * nd, dd);
-    if (!nd) DEVOUT(14, 8, dd);
-    H2D(15, lbx, (size_t)B * n, dlbx); H2D(16, ubx, (size_t)B * n, dubx);
-    H2D(17, (mi ? lbg : nullptr), (size_t)B * mi, dlbg); H2D(18, (mi ? ubg : nullptr), (size_t)B * mi, dubg);
-    DEVOUT(19, (size_t)B * n * sizeof(double), dx); DEVOUT(20, (size_t)B * (m + n) * sizeof(double), dlam);
-    DEVOUT(21, (size_t)B * sizeof(pmpc_sqp_info), dinfo);
-    pmpc_status st = fn(ctx, model, P, S, t0, tf, B, dxg, dlg, dd, dlbx, dubx, dlbg, dubg, ss, qs, dx, dlam, dinfo);
-    if (st != PMPC_OK) return st;
-    HIPCHK(hipMemcpyAsync(x, dx, (size_t)B * n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipMemcpyAsync(lam, dlam, (size_t)B * (m + n) * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipMemcpyAsync(info, dinfo, (size_t)B * sizeof(pmpc_sqp_info), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    return PMPC_OK;
+    const int nn = P * S + 1, n = (nx + nu) * nn + np, me = nx * nn, mi = ng * nn;
+    return sqp_solve_host(ctx, B, n, me + mi, nd, mi, {x_guess, lam_guess, d, lbx, ubx, lbg, ubg, x, lam, info}, [&](const SqpBuffers& v) {
+        return fn(ctx, model, P, S, t0, tf, B, v.x_guess, v.lam_guess, v.d, v.lbx, v.ubx, v.lbg, v.ubg, ss, qs, v.x, v.lam, v.info);
+    });
 }
 
 }  // extern "C"

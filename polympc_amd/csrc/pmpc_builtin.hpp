@@ -40,28 +40,27 @@ pmpc_status linearise_impl(pmpc_context* ctx, int P, int S, double t0, double tf
     const int n = dm.n, m = dm.m;
     const size_t lds = linearise_kernel_lds_bytes<Model>(P, S);
     if (lds > ctx->lds_limit) return PMPC_ERR_UNSUPPORTED_SIZE;
-    double *dvar, *dd, *dlam, *dcost, *dc, *dj, *dcg, *dlg, *dlh;
-    H2D(0, var, (size_t)B * n, dvar); H2D(1, (Model::ND ? d : nullptr), (size_t)B * Model::ND, dd); H2D(2, lam, (size_t)B * (m + n), dlam);
-    if (!Model::ND) DEVOUT(1, 8, dd);
-    DEVOUT(3, (size_t)B * 2 * sizeof(double), dcost); DEVOUT(4, (size_t)B * m * sizeof(double), dc);
-    DEVOUT(5, (size_t)B * m * n * sizeof(double), dj); DEVOUT(6, (size_t)B * n * sizeof(double), dcg);
-    DEVOUT(7, (size_t)B * n * sizeof(double), dlg); DEVOUT(8, (size_t)B * n * n * sizeof(double), dlh);
+    Staging stg(ctx);
+    const size_t Bz = (size_t)B;
+    const double *dvar = stg.in(SLOT_LIN_X, var, Bz * n), *dd = stg.in(SLOT_LIN_IN1, Model::ND ? d : nullptr, Bz * Model::ND), *dlam = stg.in(SLOT_LIN_IN2, lam, Bz * (m + n));
+    double *dcost = stg.out<double>(SLOT_LIN_COST, Bz * 2), *dc = stg.out<double>(SLOT_LIN_CONSTR, Bz * m), *dj = stg.out<double>(SLOT_LIN_JAC, Bz * m * n);
+    double *dcg = stg.out<double>(SLOT_LIN_COST_GRAD, Bz * n), *dlg = stg.out<double>(SLOT_LIN_LAG_GRAD, Bz * n), *dlh = stg.out<double>(SLOT_LIN_LAG_HESS, Bz * n * n);
+    if (!Model::ND) dd = stg.absent<double>();
+    if (!stg.ok()) return stg.status;
     HIPCHK(hipFuncSetAttribute((const void*)linearise_kernel<Model>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     Model mdl = make_model<Model>(mp, nmp);
     hipLaunchKernelGGL(linearise_kernel<Model>, dim3(B), dim3(WAVE), lds, ctx->stream, mdl, cd, B, dvar, dd, dlam, dcost, dc, dj, dcg, dlg, dlh);
     HIPCHK(hipGetLastError());
-    std::vector<double> c2((size_t)B * 2);
-    HIPCHK(hipMemcpyAsync(c2.data(), dcost, (size_t)B * 2 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (constr) HIPCHK(hipMemcpyAsync(constr, dc, (size_t)B * m * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (jac) HIPCHK(hipMemcpyAsync(jac, dj, (size_t)B * m * n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (cost_grad) HIPCHK(hipMemcpyAsync(cost_grad, dcg, (size_t)B * n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (lag_grad) HIPCHK(hipMemcpyAsync(lag_grad, dlg, (size_t)B * n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (lag_hess) HIPCHK(hipMemcpyAsync(lag_hess, dlh, (size_t)B * n * n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
+    std::vector<double> c2(Bz * 2);
+    stg.fetch(c2.data(), dcost, Bz * 2);
+    if (constr) stg.fetch(constr, dc, Bz * m);
+    if (jac) stg.fetch(jac, dj, Bz * m * n);
+    if (cost_grad) stg.fetch(cost_grad, dcg, Bz * n); if (lag_grad) stg.fetch(lag_grad, dlg, Bz * n);
+    if (lag_hess) stg.fetch(lag_hess, dlh, Bz * n * n);
+    if (stg.sync() != PMPC_OK) return stg.status;
     if (cost) for (int b = 0; b < 2 * B; ++b) cost[b] = c2[b];
     return PMPC_OK;
 }
-
 
 #define PMPC_INSTANTIATE_BUILTIN(Model)                                                                                                  \
     template pmpc_status sqp_builtin_dev<Model>(pmpc_context*, int, int, double, double, const double*, int, int, const double*,        \

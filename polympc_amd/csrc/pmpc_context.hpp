@@ -1,5 +1,5 @@
-// polympc_amd — the context object behind the opaque pmpc_context handle and the host-side staging helpers shared by the
-// translation units of libpolympc_amd.so (pmpc_api.hip and one pmpc_model_*.hip per built-in OCP).
+// polympc_amd — the context object behind the opaque pmpc_context handle, shared by the translation units of libpolympc_amd.so; the
+// host-side staging of the host-buffer entry points follows in pmpc_staging.hpp, included at the end.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <condition_variable>
@@ -74,7 +74,7 @@ struct pmpc_context {
                                    // no getenv on the launch path (ShardWorker threads would race a host program's setenv), see pmpc_internal_switch
     std::map<std::tuple<int, int, double, double>, ChebData*> cheb_cache;
     double* ws = nullptr; size_t ws_bytes = 0;       // SQP HBM workspace (H, J)
-    void* scratch[24] = {nullptr}; size_t scratch_bytes[24] = {0};  // host-buffer API staging
+    void* scratch[24] = {nullptr}; size_t scratch_bytes[24] = {0};  // host-buffer API staging (the slots: pmpc_slot, pmpc_staging.hpp)
     ShardWorker* shard_worker = nullptr;             // pmpc_sqp_solve_batch_multi: this context's persistent host thread (created on first use)
 };
 
@@ -126,21 +126,4 @@ inline pmpc_status get_cheb(pmpc_context* ctx, int P, int S, double t0, double t
     return PMPC_OK;
 }
 
-
-#define H2D(slot, host, count, devptr)                                                                        \
-    do {                                                                                                      \
-        void* p_ = nullptr;                                                                                   \
-        if (host) {                                                                                           \
-            pmpc_status st_ = ensure_scratch(ctx, slot, (size_t)(count) * sizeof(double), &p_);               \
-            if (st_ != PMPC_OK) return st_;                                                                   \
-            HIPCHK(hipMemcpyAsync(p_, host, (size_t)(count) * sizeof(double), hipMemcpyHostToDevice, ctx->stream)); \
-        }                                                                                                     \
-        devptr = (double*)p_;                                                                                 \
-    } while (0)
-#define DEVOUT(slot, bytes, devptr)                                                \
-    do {                                                                           \
-        void* p_ = nullptr;                                                        \
-        pmpc_status st_ = ensure_scratch(ctx, slot, (size_t)(bytes), &p_);         \
-        if (st_ != PMPC_OK) return st_;                                            \
-        devptr = (decltype(devptr))p_;                                             \
-    } while (0)
+#include "pmpc_staging.hpp"

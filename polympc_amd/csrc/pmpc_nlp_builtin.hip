@@ -82,7 +82,7 @@ pmpc_status pmpc_nlp_solve_batch_dev(pmpc_context* ctx, int problem, int B, cons
     PMPC_NLP_DISPATCH(problem, pmpc::nlp_launch_dev(ctx, D, B, x_guess, lam_guess, d, lbx, ubx, lbg, ubg, ss, qs, x, lam, info))
 }
 
-// host-buffer form of any pmpc_nlp_dev_fn-shaped solve (staging slots 12 .. 21, as pmpc_sqp_solve_batch_user)
+// host-buffer form of any pmpc_nlp_dev_fn-shaped solve; the checks are those of nlp_launch_dev, ahead of the first device call
 static pmpc_status nlp_solve_host(pmpc_context* ctx, pmpc_nlp_dev_fn fn, int problem, const void* model, int nx, int ne, int ni, int np, int B,
                                   const double* x_guess, const double* lam_guess, const double* d, const double* lbx, const double* ubx,
                                   const double* lbg, const double* ubg, const pmpc_sqp_settings* ss, const pmpc_qp_settings* qs, double* x,
@@ -91,22 +91,10 @@ static pmpc_status nlp_solve_host(pmpc_context* ctx, pmpc_nlp_dev_fn fn, int pro
     if (pmpc::nlp_check_settings(ss, qs) != PMPC_OK) return PMPC_ERR_INVALID_ARGUMENT;
     if (nx + ne + ni > pmpc::WAVE) return PMPC_ERR_UNSUPPORTED_SIZE;
     if (B == 0) return PMPC_OK;
-    HIPCHK(hipSetDevice(ctx->device));
-    const size_t n = nx, m = (size_t)ne + ni;
-    double *dxg, *dlg, *dd, *dlbx, *dubx, *dlbg, *dubg, *dx, *dlam; pmpc_sqp_info* dinfo;
-    H2D(12, x_guess, (size_t)B * n, dxg); H2D(13, lam_guess, (size_t)B * (m + n), dlg); H2D(14, (np ? d : nullptr), (size_t)B * np, dd);
-    H2D(15, lbx, (size_t)B * n, dlbx); H2D(16, ubx, (size_t)B * n, dubx);
-    H2D(17, (ni ? lbg : nullptr), (size_t)B * ni, dlbg); H2D(18, (ni ? ubg : nullptr), (size_t)B * ni, dubg);
-    DEVOUT(19, (size_t)B * n * sizeof(double), dx); DEVOUT(20, (size_t)B * (m + n) * sizeof(double), dlam);
-    DEVOUT(21, (size_t)B * sizeof(pmpc_sqp_info), dinfo);
-    const pmpc_status st = fn ? fn(ctx, model, B, dxg, dlg, dd, dlbx, dubx, dlbg, dubg, ss, qs, dx, dlam, dinfo)
-                              : pmpc_nlp_solve_batch_dev(ctx, problem, B, dxg, dlg, dd, dlbx, dubx, dlbg, dubg, ss, qs, dx, dlam, dinfo);
-    if (st != PMPC_OK) return st;
-    HIPCHK(hipMemcpyAsync(x, dx, (size_t)B * n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipMemcpyAsync(lam, dlam, (size_t)B * (m + n) * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipMemcpyAsync(info, dinfo, (size_t)B * sizeof(pmpc_sqp_info), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    return PMPC_OK;
+    return sqp_solve_host(ctx, B, nx, ne + ni, np, ni, {x_guess, lam_guess, d, lbx, ubx, lbg, ubg, x, lam, info}, [&](const SqpBuffers& v) {
+        return fn ? fn(ctx, model, B, v.x_guess, v.lam_guess, v.d, v.lbx, v.ubx, v.lbg, v.ubg, ss, qs, v.x, v.lam, v.info)
+                  : pmpc_nlp_solve_batch_dev(ctx, problem, B, v.x_guess, v.lam_guess, v.d, v.lbx, v.ubx, v.lbg, v.ubg, ss, qs, v.x, v.lam, v.info);
+    });
 }
 
 pmpc_status pmpc_nlp_solve_batch(pmpc_context* ctx, int problem, int B, const double* x_guess, const double* lam_guess, const double* d,
@@ -135,15 +123,13 @@ pmpc_status pmpc_nlp_linearise_batch(pmpc_context* ctx, int problem, int B, cons
     if (B == 0) return PMPC_OK;
     HIPCHK(hipSetDevice(ctx->device));
     const size_t n = nx, m = (size_t)ne + ni;
-    double *dxin, *dlam, *dd, *dc, *dg, *dj, *dcg, *dlg, *dlh;
-    H2D(0, xin, (size_t)B * n, dxin); H2D(1, lamin, (size_t)B * (m + n), dlam); H2D(2, (np ? d : nullptr), (size_t)B * np, dd);
-    dc = dg = dj = dcg = dlg = dlh = nullptr;
-    if (cost) DEVOUT(3, (size_t)B * sizeof(double), dc);
-    if (constr && m) DEVOUT(4, (size_t)B * m * sizeof(double), dg);
-    if (jac && m) DEVOUT(5, (size_t)B * m * n * sizeof(double), dj);
-    if (cost_grad) DEVOUT(6, (size_t)B * n * sizeof(double), dcg);
-    if (lag_grad) DEVOUT(7, (size_t)B * n * sizeof(double), dlg);
-    if (lag_hess) DEVOUT(8, (size_t)B * n * n * sizeof(double), dlh);
+    Staging stg(ctx);
+    const double *dxin = stg.in(SLOT_LIN_X, xin, B * n), *dlam = stg.in(SLOT_LIN_IN1, lamin, B * (m + n)), *dd = stg.in(SLOT_LIN_IN2, np ? d : nullptr, (size_t)B * np);
+    double *dc = cost ? stg.out<double>(SLOT_LIN_COST, B) : nullptr, *dg = constr && m ? stg.out<double>(SLOT_LIN_CONSTR, B * m) : nullptr;
+    double *dj = jac && m ? stg.out<double>(SLOT_LIN_JAC, B * m * n) : nullptr, *dcg = cost_grad ? stg.out<double>(SLOT_LIN_COST_GRAD, B * n) : nullptr;
+    double *dlg = lag_grad ? stg.out<double>(SLOT_LIN_LAG_GRAD, B * n) : nullptr, *dlh = lag_hess ? stg.out<double>(SLOT_LIN_LAG_HESS, B * n * n) : nullptr;
+    if (!np) dd = stg.absent<double>();
+    if (!stg.ok()) return stg.status;
     pmpc_status st;
     switch (problem) {
         case PMPC_NLP_CONSTRAINED_ROSENBROCK: st = pmpc::nlp_linearise_dev(ctx, pmpc::NlpConstrainedRosenbrock{}, B, dxin, dlam, dd, dc, dg, dj, dcg, dlg, dlh); break;
@@ -152,14 +138,10 @@ pmpc_status pmpc_nlp_linearise_batch(pmpc_context* ctx, int problem, int B, cons
         default: st = pmpc::nlp_linearise_dev(ctx, pmpc::NlpHS071{}, B, dxin, dlam, dd, dc, dg, dj, dcg, dlg, dlh); break;
     }
     if (st != PMPC_OK) return st;
-    if (dc) HIPCHK(hipMemcpyAsync(cost, dc, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (dg) HIPCHK(hipMemcpyAsync(constr, dg, (size_t)B * m * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (dj) HIPCHK(hipMemcpyAsync(jac, dj, (size_t)B * m * n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (dcg) HIPCHK(hipMemcpyAsync(cost_grad, dcg, (size_t)B * n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (dlg) HIPCHK(hipMemcpyAsync(lag_grad, dlg, (size_t)B * n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (dlh) HIPCHK(hipMemcpyAsync(lag_hess, dlh, (size_t)B * n * n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    return PMPC_OK;
+    if (dc) stg.fetch(cost, dc, B); if (dg) stg.fetch(constr, dg, B * m);
+    if (dj) stg.fetch(jac, dj, B * m * n); if (dcg) stg.fetch(cost_grad, dcg, B * n);
+    if (dlg) stg.fetch(lag_grad, dlg, B * n); if (dlh) stg.fetch(lag_hess, dlh, B * n * n);
+    return stg.sync();
 }
 
 }  // extern "C"

@@ -4,6 +4,7 @@
 // pipeline's slots); the other ADMM vectors live behind the factor in the per-QP HBM workspace.
 #include <hip/hip_runtime.h>
 #include "../../include/polympc_amd.h"
+#include "pmpc_context.hpp"
 #include "pmpc_qp_big.hpp"
 
 using namespace pmpc;
@@ -37,13 +38,4 @@ extern "C" size_t pmpc_internal_qp_big_ws_doubles(int n, int m) { return BigKkt:
 extern "C" size_t pmpc_internal_qp_big_lds_bytes(int n, int m) {
     return (QpLds::doubles_xy(n, m) + (size_t)(n + m) + BigKkt::LDS_DOUBLES) * sizeof(double);
 }
-// launches on `stream` with the per-QP workspaces at Kws; 0 on success, -1 on a launch error
-extern "C" int pmpc_internal_qp_big_launch(void* stream, double* Kws, int B, int n, int m, const double* H, const double* h, const double* A,
-                                           const double* Alb, const double* Aub, const double* xlb, const double* xub, const double* x0,
-                                           const double* y0, const pmpc_qp_settings* s, double* x, double* y, pmpc_qp_info* info) {
-    const size_t lds = pmpc_internal_qp_big_lds_bytes(n, m);
-    if (hipFuncSetAttribute((const void*)qp_boxadmm_big_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return -1;
-    hipLaunchKernelGGL(qp_boxadmm_big_kernel, dim3(B), dim3(WAVE), lds, (hipStream_t)stream, B, n, m, H, h, A, Alb, Aub, xlb, xub, x0, y0, *s, Kws,
-                       x, y, info);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
+extern "C" QpBigKernel pmpc_internal_qp_big_kernel(void) { return qp_boxadmm_big_kernel; }

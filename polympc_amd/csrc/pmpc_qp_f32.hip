@@ -351,80 +351,27 @@ __global__ __launch_bounds__(64) void qp_admm_f32_kernel(int B, int n, int m, co
 
 }  // namespace
 
-extern "C" {
-
-static pmpc_status f32_solve_dev(bool osqp, pmpc_context* ctx, int B, int n, int m, const float* H, const float* h, const float* A, const float* Alb,
-                                 const float* Aub, const float* xlb, const float* xub, const float* x0, const float* y0,
-                                 const pmpc_qp_settings* settings, float* x, float* y, pmpc_qp_info* info) {
-    if (!ctx || B < 0 || n < 1 || m < 0 || !H || !h || !xlb || !xub || !settings || !x || !y || !info) return PMPC_ERR_INVALID_ARGUMENT;
-    if (m > 0 && (!A || !Alb || !Aub)) return PMPC_ERR_INVALID_ARGUMENT;
-    if ((x0 == nullptr) != (y0 == nullptr)) return PMPC_ERR_INVALID_ARGUMENT;
-    if (settings->linear_solver != 0) return PMPC_ERR_INVALID_ARGUMENT;   // the static order only
-    if (B == 0) return PMPC_OK;
+template <bool OSQP> static pmpc_status f32_solve_dev(QpArgsT<float> a) {
+    const pmpc_status chk = check_qp_args(a, EMPTY_AFTER_SOLVER, SOLVER_STATIC_ONLY);
+    if (chk != PMPC_OK || a.B == 0) return chk;
+    pmpc_context* ctx = a.ctx;
+    const int n = a.n, m = a.m;
     HIPCHK(hipSetDevice(ctx->device));
-    const size_t lds = (osqp ? F32AdmmLds::floats(n, m) : F32Lds::floats(n, m)) * sizeof(float);
-    if ((osqp ? 2 * n + m : n + m) > 2 * WAVE || lds > ctx->lds_limit) return PMPC_ERR_UNSUPPORTED_SIZE;   // two KKT rows per lane, the matrix in LDS
-    auto kern = osqp ? qp_admm_f32_kernel : qp_boxadmm_f32_kernel;
+    const size_t lds = (OSQP ? F32AdmmLds::floats(n, m) : F32Lds::floats(n, m)) * sizeof(float);
+    if ((OSQP ? 2 * n + m : n + m) > 2 * WAVE || lds > ctx->lds_limit) return PMPC_ERR_UNSUPPORTED_SIZE;   // two KKT rows per lane, the matrix in LDS
+    auto kern = OSQP ? qp_admm_f32_kernel : qp_boxadmm_f32_kernel;
     HIPCHK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     PMPC_POISON_DEVICE(ctx);
-    hipLaunchKernelGGL(kern, dim3(B), dim3(WAVE), lds, ctx->stream, B, n, m, H, h, A, Alb, Aub, xlb, xub, x0, y0, *settings, x, y, info);
+    hipLaunchKernelGGL(kern, dim3(a.B), dim3(WAVE), lds, ctx->stream, a.B, n, m, a.H, a.h, a.A, a.Alb, a.Aub, a.xlb, a.xub, a.x0, a.y0, *a.settings, a.x, a.y, a.info);
     HIPCHK(hipGetLastError());
     return PMPC_OK;
 }
-pmpc_status pmpc_qp_boxadmm_solve_batch_f32_dev(pmpc_context* ctx, int B, int n, int m, const float* H, const float* h, const float* A, const float* Alb,
-                                                const float* Aub, const float* xlb, const float* xub, const float* x0, const float* y0,
-                                                const pmpc_qp_settings* settings, float* x, float* y, pmpc_qp_info* info) {
-    return f32_solve_dev(false, ctx, B, n, m, H, h, A, Alb, Aub, xlb, xub, x0, y0, settings, x, y, info);
-}
-pmpc_status pmpc_qp_admm_solve_batch_f32_dev(pmpc_context* ctx, int B, int n, int m, const float* H, const float* h, const float* A, const float* Alb,
-                                             const float* Aub, const float* xlb, const float* xub, const float* x0, const float* y0,
-                                             const pmpc_qp_settings* settings, float* x, float* y, pmpc_qp_info* info) {
-    return f32_solve_dev(true, ctx, B, n, m, H, h, A, Alb, Aub, xlb, xub, x0, y0, settings, x, y, info);
-}
 
-static pmpc_status f32_solve_host(bool osqp, pmpc_context* ctx, int B, int n, int m, const float* H, const float* h, const float* A, const float* Alb,
-                                  const float* Aub, const float* xlb, const float* xub, const float* x0, const float* y0,
-                                  const pmpc_qp_settings* settings, float* x, float* y, pmpc_qp_info* info) {
-    if (!ctx || B < 0 || n < 1 || m < 0 || !H || !h || !xlb || !xub || !settings || !x || !y || !info) return PMPC_ERR_INVALID_ARGUMENT;
-    if (m > 0 && (!A || !Alb || !Aub)) return PMPC_ERR_INVALID_ARGUMENT;
-    if ((x0 == nullptr) != (y0 == nullptr)) return PMPC_ERR_INVALID_ARGUMENT;
-    if (B == 0) return PMPC_OK;
-    HIPCHK(hipSetDevice(ctx->device));
-    const size_t Bz = (size_t)B;
-    const void* host[9] = {H, h, A, Alb, Aub, xlb, xub, x0, y0};
-    const size_t count[9] = {Bz * n * n, Bz * n, Bz * m * n, Bz * m, Bz * m, Bz * n, Bz * n, Bz * n, Bz * (n + m)};
-    float* dev[9] = {nullptr};
-    for (int k = 0; k < 9; ++k) {
-        if (!host[k] || count[k] == 0) continue;
-        void* p = nullptr;
-        const pmpc_status st = ensure_scratch(ctx, k, count[k] * sizeof(float), &p);
-        if (st != PMPC_OK) return st;
-        HIPCHK(hipMemcpyAsync(p, host[k], count[k] * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-        dev[k] = (float*)p;
-    }
-    void *dx = nullptr, *dy = nullptr, *di = nullptr;
-    pmpc_status st = ensure_scratch(ctx, 9, Bz * n * sizeof(float), &dx); if (st != PMPC_OK) return st;
-    st = ensure_scratch(ctx, 10, Bz * (n + m) * sizeof(float), &dy); if (st != PMPC_OK) return st;
-    st = ensure_scratch(ctx, 11, Bz * sizeof(pmpc_qp_info), &di); if (st != PMPC_OK) return st;
-    if (m == 0) { dev[2] = dev[3] = dev[4] = (float*)dx; }   // never read (m = 0), but the device entry wants non-null pointers only when m > 0
-    st = f32_solve_dev(osqp, ctx, B, n, m, dev[0], dev[1], dev[2], dev[3], dev[4], dev[5], dev[6], dev[7], dev[8], settings,
-                       (float*)dx, (float*)dy, (pmpc_qp_info*)di);
-    if (st != PMPC_OK) return st;
-    HIPCHK(hipMemcpyAsync(x, dx, Bz * n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipMemcpyAsync(y, dy, Bz * (n + m) * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipMemcpyAsync(info, di, Bz * sizeof(pmpc_qp_info), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    return PMPC_OK;
-}
-pmpc_status pmpc_qp_boxadmm_solve_batch_f32(pmpc_context* ctx, int B, int n, int m, const float* H, const float* h, const float* A, const float* Alb,
-                                            const float* Aub, const float* xlb, const float* xub, const float* x0, const float* y0,
-                                            const pmpc_qp_settings* settings, float* x, float* y, pmpc_qp_info* info) {
-    return f32_solve_host(false, ctx, B, n, m, H, h, A, Alb, Aub, xlb, xub, x0, y0, settings, x, y, info);
-}
-pmpc_status pmpc_qp_admm_solve_batch_f32(pmpc_context* ctx, int B, int n, int m, const float* H, const float* h, const float* A, const float* Alb,
-                                         const float* Aub, const float* xlb, const float* xub, const float* x0, const float* y0,
-                                         const pmpc_qp_settings* settings, float* x, float* y, pmpc_qp_info* info) {
-    return f32_solve_host(true, ctx, B, n, m, H, h, A, Alb, Aub, xlb, xub, x0, y0, settings, x, y, info);
-}
+extern "C" {
+
+pmpc_status pmpc_qp_boxadmm_solve_batch_f32_dev(PMPC_QP_PARAMS(float)) { return f32_solve_dev<false>(PMPC_QP_ARGS(float)); }
+pmpc_status pmpc_qp_admm_solve_batch_f32_dev(PMPC_QP_PARAMS(float)) { return f32_solve_dev<true>(PMPC_QP_ARGS(float)); }
+pmpc_status pmpc_qp_boxadmm_solve_batch_f32(PMPC_QP_PARAMS(float)) { return qp_solve_host<float>(PMPC_QP_ARGS(float), f32_solve_dev<false>, EMPTY_AFTER_BLOCKS, SOLVER_STATIC_ONLY); }
+pmpc_status pmpc_qp_admm_solve_batch_f32(PMPC_QP_PARAMS(float)) { return qp_solve_host<float>(PMPC_QP_ARGS(float), f32_solve_dev<true>, EMPTY_AFTER_BLOCKS, SOLVER_STATIC_ONLY); }
 
 }  // extern "C"

@@ -96,7 +96,8 @@ def test_bench_rejects_a_launcher_mismatch():
 
 def test_argument_validation_without_a_device():
     """Entry points reject bad arguments before touching the GPU (so this runs on a CPU box): NULL context, and — with any non-NULL
-    context pointer never dereferenced on these paths — max_iter < 1 and a missing static-parameter array for a model with ND > 0."""
+    context pointer never dereferenced on these paths — max_iter < 1 and a missing static-parameter array for a model with ND > 0. The
+    host-buffer wrappers keep the rule too: they share one argument check per family with their _dev twins and run it before the first device call."""
     import ctypes as C
     import polympc_amd as pa
     L = pa.lib()
@@ -111,3 +112,46 @@ def test_argument_validation_without_a_device():
     assert f(*args(fake, None, ss)) == 1                      # ND = 1 (robot) and d == NULL
     s0 = pa.sqp_settings_default(); s0.max_iter = 0
     assert f(*args(fake, one, s0)) == 1                       # nothing would be solved
+    # ---- the host-buffer wrappers keep the same rule: every refusal below is answered before the context is touched
+    P_ = C.POINTER(C.c_double)
+    dbl = lambda v: C.cast(v, P_)
+    g = L.pmpc_sqp_solve_batch
+    g.restype = C.c_int
+    g.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, P_, C.c_int, C.c_int] + [P_] * 7 + \
+                 [C.POINTER(pa.SQPSettings), C.POINTER(pa.QPSettings), P_, P_, C.c_void_p]
+    hargs = lambda d, s: (fake, 0, 6, 1, 0.0, 2.0, None, 0, 1, None, None, d, dbl(one), dbl(one), None, None, C.byref(s), C.byref(qs), dbl(one), dbl(one), info)
+
+    def sqp_with(**kw):
+        s = pa.sqp_settings_default()
+        for k, v in kw.items():
+            setattr(s, k, v)
+        return s
+    assert g(*hargs(None, ss)) == 1                                        # robot model with d == NULL
+    for bad in (dict(max_iter=0), dict(kkt_form=3), dict(regularisation=3), dict(iteration_trace=8, iteration_trace_capacity=0)):
+        assert g(*hargs(dbl(one), sqp_with(**bad))) == 1, bad
+        assert f(*args(fake, one, sqp_with(**bad))) == 1, bad              # (and the _dev twin: one check for both)
+    # QP wrappers, fp64 and fp32, boxADMM and OSQP form, host and _dev: m > 0 with A == NULL; x0 without y0; boxADMM fp64: linear_solver = 2
+    q = pa.qp_settings_default()
+    flt = (C.c_float * 64)()
+    for name, buf, T_ in [("pmpc_qp_boxadmm_solve_batch", one, C.c_double), ("pmpc_qp_admm_solve_batch", one, C.c_double),
+                          ("pmpc_qp_boxadmm_solve_batch_f32", flt, C.c_float), ("pmpc_qp_admm_solve_batch_f32", flt, C.c_float)]:
+        for suffix in ("", "_dev"):
+            e = getattr(L, name + suffix)
+            e.restype = C.c_int
+            PT = C.POINTER(T_)
+            e.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int] + [PT] * 9 + [C.POINTER(pa.QPSettings)] + [PT] * 2 + [C.c_void_p]
+            p = C.cast(buf, PT)
+            call = lambda m, A, x0, y0, s: e(fake, 1, 2, m, p, p, A, p, p, p, p, x0, y0, C.byref(s), p, p, info)
+            assert call(1, None, None, None, q) == 1, name + suffix        # m > 0 and A == NULL
+            assert call(1, p, p, None, q) == 1, name + suffix              # x0 without y0
+            assert call(0, None, None, p, q) == 1, name + suffix           # y0 without x0 (m = 0: A may be NULL)
+    q2 = pa.qp_settings_default(); q2.linear_solver = 2
+    for name in ("pmpc_qp_boxadmm_solve_batch", "pmpc_qp_boxadmm_solve_batch_dev"):
+        p = dbl(one)
+        assert getattr(L, name)(fake, 1, 2, 1, p, p, p, p, p, p, p, None, None, C.byref(q2), p, p, info) == 1, name
+    # generic NLP: a setting nlp_check_settings refuses
+    nl = L.pmpc_nlp_solve_batch
+    nl.restype = C.c_int
+    nl.argtypes = [C.c_void_p, C.c_int, C.c_int] + [P_] * 7 + [C.POINTER(pa.SQPSettings), C.POINTER(pa.QPSettings), P_, P_, C.c_void_p]
+    for bad in (dict(hessian_update=1), dict(line_search=1), dict(regularisation=3)):
+        assert nl(fake, pa.NLP_HS071, 1, None, None, None, None, None, None, None, C.byref(sqp_with(**bad)), C.byref(qs), dbl(one), dbl(one), info) == 1, bad

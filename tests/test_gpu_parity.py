@@ -30,7 +30,7 @@ def _mat(Hc, n, m=None):
 BIG_KKT_MIN_ROWS = 96   # pmpc_launch.hpp: from this many KKT rows the fused SQP kernel keeps its factor in HBM (blocked tile LDL^T)
 
 
-QP_BIG_MIN_ROWS = 112   # pmpc_api.hip: the QP entry point's threshold for the same kernel family
+QP_BIG_MIN_ROWS = 112   # pmpc_qp_entry.hip: the QP entry point's threshold for the same kernel family
 
 
 def _lds_order(oracle, rows, qp_entry=False, ruiz=False, kkt_form=0):
@@ -46,7 +46,7 @@ def _lds_order(oracle, rows, qp_entry=False, ruiz=False, kkt_form=0):
 
 
 REG2_QP_SHAPES = ((66, 44), (55, 33), (45, 27), (50, 30), (60, 36), (65, 39), (54, 36), (60, 40), (80, 48), (75, 45), (72, 48))
-REG1_QP_SHAPES = ((35, 21), (20, 12), (25, 15), (30, 18), (40, 24), (24, 16), (30, 20), (36, 24))   # one KKT row per lane (pmpc_api.hip)   # QP entry point: two-rows-per-lane register specialisations (pmpc_qp_reg2.hip)
+REG1_QP_SHAPES = ((35, 21), (20, 12), (25, 15), (30, 18), (40, 24), (24, 16), (30, 20), (36, 24))   # one KKT row per lane (pmpc_qp_entry.hip)   # QP entry point: two-rows-per-lane register specialisations (pmpc_qp_reg2.hip)
 
 
 REG_NODE_COUNTS = (3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16)   # grids of the built-in models with register-resident SQP kernels (pmpc_launch.hpp, pmpc_grids.hpp)

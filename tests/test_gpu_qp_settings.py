@@ -1,6 +1,6 @@
 """The QP entry points under every setting that moves the control flow of boxADMM / ADMM, on every kernel family.
 
-pmpc_qp_boxadmm_solve_batch is served by five separately written kernels, chosen by shape (pmpc_api.hip): one KKT row per lane (pmpc_qp_reg.hpp, plus its
+pmpc_qp_boxadmm_solve_batch is served by five separately written kernels, chosen by shape (pmpc_qp_entry.hip): one KKT row per lane (pmpc_qp_reg.hpp, plus its
 redo launch), two rows per lane (pmpc_qp_reg2.hpp), the LDS-resident static LDL^T and its pivoted twin for linear_solver = 1 (pmpc_qp.hpp) and the HBM-factor
 tile LDL^T (pmpc_qp_big.hpp); beside them stand the OSQP-form qp_admm_kernel and the two single-precision kernels (pmpc_qp_f32.hip). Each carries its own
 copy of the relaxation with alpha, the check_termination / adaptive_rho_interval countdowns, the adaptive-rho trigger, the refactorisation, the
@@ -39,7 +39,7 @@ FAMILY_CASES = [("reg1", 35, 21, 129, 0), ("reg1", 20, 12, 9, 0),
 
 
 def _family_of(n, m, linear_solver):
-    """pmpc_api.hip, pmpc_qp_boxadmm_solve_batch_dev: which kernel serves (n, m)."""
+    """pmpc_qp_entry.hip, plan_qp: which kernel serves (n, m)."""
     if linear_solver:
         return "pivoted"
     if (n, m) in T.REG1_QP_SHAPES:
@@ -191,7 +191,7 @@ LDS_BYTES = 160 * 1024   # gfx950: LDS per CU = the most one workgroup may alloc
 
 
 def _admm_lds_bytes(n, m):
-    """pmpc_api.hip: QpLds::doubles(n, m + n) * sizeof(double) — the stacked (2n+m)-row factor and the vectors of qp_admm_kernel (pmpc_qp.hpp)."""
+    """pmpc_qp_entry.hip: QpLds::doubles(n, m + n) * sizeof(double) — the stacked (2n+m)-row factor and the vectors of qp_admm_kernel (pmpc_qp.hpp)."""
     M = m + n
     N = n + M
     return 8 * (N * (N + 1) // 2 + 2 * 64 + 3 * n + N + 5 * M + 2 * n + N + 2 * N + M + N + 8)
