@@ -102,6 +102,27 @@ __device__ __forceinline__ void swap16(double& a, double& b) {
     a = __hiloint2double(hi[0], lo[0]); b = __hiloint2double(hi[1], lo[1]);
 }
 
+// the lane id re-materialised next to a batch of loads (two v_mbcnt tied to the opaque zero `zo`): a long-lived per-lane offset is spilled, and its
+// scratch reload in the middle of the batch waits on vmcnt for every load issued before it
+__device__ __forceinline__ unsigned lane_id_near(int zo) {
+    unsigned l;
+    asm("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=&v"(l) : "v"(zo));
+    return l;
+}
+
+// DIRECT TILE STAGING (RegKkt::invert, constraint-first mode): the KKT tiles and the operands of the rank-m update are loaded from the stacked
+// [H; A] workspace straight in MFMA layout, instead of row-per-lane and transposed through LDS. Developer switch for the A/B of its stages
+// (profiles/*_ab_direct_tile_staging.txt): 0 the row path; 1 the all-primal tile components; 2 every tile component; 3 the rank-m operands too.
+#ifndef PMPC_DIRECT_STAGING
+#define PMPC_DIRECT_STAGING 3
+#endif
+// The tile source of that path: ws = the (NPIV + MC) x NPIV column-major array [H; A] (leading dimension N), H BITWISE SYMMETRIC (entry (i, j) of
+// the primal block is read as H(j, i): the sixteen lanes of a tile row then read one 128-byte line). kcol: the row path's loader (stages 0 .. 2).
+template <class KCol>
+struct StackedTileSource { const double* ws; KCol kcol; };
+template <class T> struct is_stacked_tile_source { static constexpr bool value = false; };
+template <class KCol> struct is_stacked_tile_source<StackedTileSource<KCol>> { static constexpr bool value = true; };
+
 template <int N>
 struct RegKkt {
     // W = -K^{-1} in mat-vec layout: lane 16*r + c holds  a[16*q + j] = W(16*q + c, 16*r + j)  (q < NT, j < 16; zero where the
@@ -238,17 +259,72 @@ struct RegKkt {
         // of X, beyond the exchange rows) and is written BEFORE the loads are issued: held in a register it was spilled,
         // and a scratch reload waits on vmcnt behind every outstanding load.
         X[64 * SX + ln] = diag;
+        // DIRECT (a StackedTileSource in place of kcol, see PMPC_DIRECT_STAGING): component r of tile (R, C) is entry (i, j) = (16R + 4r + lr, 16C + lc) of
+        //   primal row i:      ws[i*N + j]  = H(j, i) (= H(i, j) bitwise) for j < NPIV, A(j - NPIV, i) beyond — scaled by -rho_j there (diagonal tiles only);
+        //   constraint row i:  ws[j*N + i]  = A(i - NPIV, j), scaled by -rho_i;  columns j >= NPIV: exact zeros;  padding rows i >= N: row 0, as the row path's clamp;
+        // a per-lane base (lr*N + lc or lc*N + lr) plus a compile-time constant. rho by row / by column comes from the LDS vector RH (one write, broadcast reads).
+        // Everything lane-dependent is a select (address or value), never a branch. The operands of the rank-m update (stage 3) are loaded in the same batch.
+        constexpr bool DIRECT = is_stacked_tile_source<KCol>::value;
+        constexpr int DS = DIRECT ? PMPC_DIRECT_STAGING : 0;
+        static_assert(!DIRECT || (CF && !EST && BK * SK + XSZ + 64 <= TRI), "direct tile staging: constraint-first mode without the conditioning gate");
+        constexpr int MCD = N - NPIV, KSD = (MCD + 3) / 4, NTPD = (NPIV + 15) / 16;
+        double* RH = st + BK * SK + XSZ;   // rho of every lane (free until the final conversion)
+        if constexpr (DS >= 2) RH[ln] = rho_self;
+        auto rowsP = [](int R, int r) constexpr { return 16 * R + 4 * r + 3 < NPIV; };    // the four rows of component r of tile row R: all primal
+        auto rowsC = [](int R, int r) constexpr { return 16 * R + 4 * r >= NPIV; };       // ... none primal
+        auto colsP = [](int C) constexpr { return 16 * C + 15 < NPIV; };                  // the sixteen columns of tile column C: all primal
+        auto direct = [&](int R, int C, int r) constexpr { return DS >= 2 || (DS == 1 && rowsP(R, r) && colsP(C)); };
         sched_fence();
         int z = 0;
         asm volatile("" : "+v"(z));
+        auto&& rowload = [&]() -> auto& { if constexpr (DIRECT) return kcol.kcol; else return kcol; }();
+        if constexpr (DS < 2) {
 #pragma unroll
-        for (int j = 0; j < NP; ++j) a[j] = (j < N) ? kcol(j < N ? j : 0, z) : 0.0;
+            for (int j = 0; j < NP; ++j) a[j] = (j < N) ? rowload(j < N ? j : 0, z) : 0.0;
+        } else if constexpr (DS == 2) {   // the raw A columns of the rank-m update
+#pragma unroll
+            for (int j = NPIV; j < N; ++j) a[j] = rowload(j, z);
+        }
+        [[maybe_unused]] double ov[DS == 3 ? KSD * NTPD : 1];
+        if constexpr (DS >= 1) {
+            const unsigned l = lane_id_near(z), dlr = l >> 4, dlc = l & 15;
+            unsigned bP = dlr * N + dlc + (unsigned)z, bC = dlc * N + dlr + (unsigned)z;
+            asm("" : "+v"(bP));
+            asm("" : "+v"(bC));
+#pragma unroll
+            for (int R = 0; R < NT; ++R)
+#pragma unroll
+                for (int C = 0; C <= R; ++C)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        if (!direct(R, C, r)) continue;
+                        const int i0 = 16 * R + 4 * r, j0 = 16 * C;
+                        // primal rows: column j < N always holds below the diagonal tile of a primal tile row; clamp in the diagonal tile if it reaches past N
+                        const unsigned oP = (j0 + 15 < N) ? bP + (unsigned)(i0 * N + j0) : (j0 + dlc < (unsigned)N ? bP + (unsigned)(i0 * N + j0) : 0u);
+                        // constraint rows: column clamped to the primal block, row clamped to the workspace
+                        const unsigned iC = (i0 + 3 < N) ? bC + (unsigned)i0 : (i0 >= N ? bC - dlr : (i0 + dlr < (unsigned)N ? bC + (unsigned)i0 : bC - dlr));
+                        const unsigned oC = colsP(C) ? iC + (unsigned)(j0 * N) : (j0 + dlc < (unsigned)NPIV ? iC + (unsigned)(j0 * N) : 0u);
+                        const unsigned o = rowsP(R, r) ? oP : (rowsC(R, r) ? oC : (i0 + dlr < (unsigned)NPIV ? oP : oC));
+                        T[R][C][r] = kcol.ws[o];
+                    }
+            if constexpr (DS == 3) {   // A(4s + lr, 16R + lc) at (16R + lc)*N + NPIV + 4s + lr: the operand layout of the rank-m update
+#pragma unroll
+                for (int s2 = 0; s2 < KSD; ++s2)
+#pragma unroll
+                    for (int R = 0; R < NTPD; ++R) {
+                        const bool in = (4 * s2 + 3 < MCD || 4 * s2 + dlr < (unsigned)MCD) && (16 * R + 15 < NPIV || 16 * R + dlc < (unsigned)NPIV);
+                        const unsigned o = in ? bC + (unsigned)(16 * R * N + NPIV + 4 * s2) : 0u;
+                        ov[s2 * NTPD + R] = kcol.ws[o];
+                    }
+            }
+        }
         sched_fence();
         const bool isPl = ln < NPIV;
-        if constexpr (CF) {   // constraint lanes: row NPIV + j of the swept matrix is -rho_j A_j
+        if constexpr (CF && DS < 2) {   // constraint lanes: row NPIV + j of the swept matrix is -rho_j A_j
 #pragma unroll
             for (int j = 0; j < NPIV; ++j) { const double sc = -(rho_self * a[j]); a[j] = isPl ? a[j] : sc; }
         }
+        if constexpr (DS < 2) {
 #pragma unroll
         for (int g = 0; g < NP / SG; ++g) {
 #pragma unroll
@@ -264,10 +340,34 @@ struct RegKkt {
 #pragma unroll
                 for (int R = g / 2; R < NT; ++R)
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) T[R][g / 2][r] = X[(16 * R + lr + 4 * r) * SX + (lc & 7)];
+                    for (int r = 0; r < 4; ++r) if (!direct(R, g / 2, r)) T[R][g / 2][r] = X[(16 * R + lr + 4 * r) * SX + (lc & 7)];
             }
             lds_order();
             sched_fence();
+        }
+        } else {   // scale the directly loaded components
+            lds_order();
+#pragma unroll
+            for (int R = 0; R < NT; ++R) {
+                const double rhoc = (16 * R < NPIV && 16 * R + 15 >= NPIV) ? RH[16 * R + lc] : 0.0;   // rho_j by column: the diagonal tile that mixes primal and constraint rows
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int i0 = 16 * R + 4 * r;
+                    const bool rowP = rowsP(R, r) || (!rowsC(R, r) && i0 + lr < NPIV);
+                    const double rhor = rowsP(R, r) ? 0.0 : RH[i0 + lr];                               // rho_i by row
+#pragma unroll
+                    for (int C = 0; C <= R; ++C) {
+                        const int j0 = 16 * C;
+                        const double v = T[R][C][r];
+                        // primal row: raw below NPIV, -rho_j A(j, i) in [NPIV, N), zero beyond
+                        const double vP = colsP(C) ? v : (j0 + lc < NPIV ? v : ((j0 + 15 < N || j0 + lc < N) ? -(rhoc * v) : 0.0));
+                        // constraint (and padding) row: -rho_i A(i, j) below NPIV, zero beyond
+                        const double sc = -(rhor * v);
+                        const double vC = colsP(C) ? sc : (j0 + lc < NPIV ? sc : 0.0);
+                        T[R][C][r] = rowsP(R, r) ? vP : (rowsC(R, r) ? vC : (rowP ? vP : vC));
+                    }
+                }
+            }
         }
         // diagonal patch: entry (16R + lc, 16R + lc) of tile (R, R) sits in component lc/4 of the lanes with lc = lr + 4*(lc/4)
 #pragma unroll
@@ -279,6 +379,25 @@ struct RegKkt {
         lds_order();
         if constexpr (CF) {   // rank-(N - NPIV) update of the primal tiles: T(a, b) <- fma(rho_j A(j, a), A(j, b), T(a, b)), j ascending (one k-step of the matrix cores per 4 constraints)
             constexpr int MC = N - NPIV, KS = (MC + 3) / 4, NTP = (NPIV + 15) / 16;
+            if constexpr (DS == 3) {   // operands straight from the batch above: bv = A(4s + lr, 16R + lc) on primal columns, av = rho_j * bv, zeros elsewhere
+#pragma unroll
+                for (int s2 = 0; s2 < KS; ++s2) {
+                    const bool jin = 4 * s2 + 3 < MC || 4 * s2 + lr < MC;
+                    const double rj = RH[NPIV + (jin ? 4 * s2 + lr : 0)];
+                    double av[NTP], bv[NTP];
+#pragma unroll
+                    for (int R = 0; R < NTP; ++R) {
+                        const bool in = jin && (16 * R + 15 < NPIV || 16 * R + lc < NPIV);
+                        const double raw = ov[s2 * NTP + R], pa = rj * raw;
+                        av[R] = in ? pa : 0.0; bv[R] = in ? raw : 0.0;
+                    }
+#pragma unroll
+                    for (int R = 0; R < NTP; ++R)
+#pragma unroll
+                        for (int C = 0; C <= R; ++C) T[R][C] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[R], bv[C], T[R][C], 0, 0, 0);
+                    sched_fence();
+                }
+            } else {
 #pragma unroll
             for (int s2 = 0; s2 < KS; ++s2) {
 #pragma unroll
@@ -300,6 +419,7 @@ struct RegKkt {
                     for (int C = 0; C <= R; ++C) T[R][C] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[R], bv[C], T[R][C], 0, 0, 0);
                 sched_fence();
                 lds_order();
+            }
             }
         }
         pre(T, PA, PB, ln, lr, lc);
@@ -581,12 +701,17 @@ __device__ __forceinline__ void boxadmm_solve_reg(const double* __restrict__ H, 
             // the flag) and the launcher's redo launch solves it in the full KKT form (LDS-resident static LDL^T). Wave-uniform; restated by the CPU checker.
             // (A second, full-sweep instantiation of invert() as an in-kernel fallback cost the headline kernel 87 spilled registers; a per-pivot
             // running minimum inside the sweep 60 more SGPR spills kernel-wide, +6 % on the bench line: both dropped.)
-            const bool tripped = K.template invert<NN, GATE>(ln, tr, kdiag, [&](int j, int z) -> double {
+            auto kcol = [&](int j, int z) -> double {
                 if (j < NN) { if constexpr (SYMLOWER) return KrowLower(j < NN ? j : 0, z); else return Krow(j < NN ? j : 0, z); }
                 const double v = Acol(j >= NN ? j - NN : 0, z);   // every primal lane: column `lane` of A is its operand of the rank-m update
                 if constexpr (STACKED) return lane_near(z) < (unsigned)NN ? v : 0.0;
                 return isP ? v : 0.0;
-            }, tm, rhov);
+            };
+            // Direct tile staging where its preconditions hold: the stacked workspace of the fused SQP kernels with an H they wrote bitwise symmetric (dense
+            // BFGS, exact Hessian) and no conditioning gate. SYMLOWER (block BFGS, Ruiz-scaled H) and the caller's H of the QP entry kernels keep the row path.
+            bool tripped;
+            if constexpr (STACKED && !SYMLOWER && !GATE && PMPC_DIRECT_STAGING != 0) tripped = K.template invert<NN, GATE>(ln, tr, kdiag, StackedTileSource<decltype(kcol)>{H, kcol}, tm, rhov);
+            else tripped = K.template invert<NN, GATE>(ln, tr, kdiag, kcol, tm, rhov);
             if constexpr (GATE) { if (tripped) { status = GAVE_UP; running = false; if (dbg) dbg[0] += clock64() - f0; break; } }
             if (dbg) dbg[0] += clock64() - f0;
         }
