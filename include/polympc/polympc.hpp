@@ -319,6 +319,33 @@ public:
         }
         return st;
     }
+    // The same solve with the instances of highest priority dispatched first (pmpc_sqp_solve_batch_prioritised): priority[b] is a hint of the work
+    // instance b will need, e.g. iter_weight * iter + qp_solver_iter of its last solve; the results are those of solve(), bit for bit. Built-in OCPs
+    // on one device. Per-instance device state addressed by position does not travel with a permuted batch: the carried LSFilter
+    // (line_search = 1) and iteration callbacks are refused, as is a batch with set_devices().
+    pmpc_status solve(const std::vector<int>& priority) noexcept {
+        if ((int)priority.size() != B || !m_multi.empty() || m_settings.iteration_callback != nullptr || m_settings.line_search != 0)
+            return last_error() = PMPC_ERR_INVALID_ARGUMENT;
+        pmpc_context* ctx = context();
+        if (!ctx) return last_error();
+        pmpc_sqp_settings ss;
+        pmpc_sqp_settings_default(&ss);
+        ss.tau = m_settings.tau; ss.eta = m_settings.eta; ss.rho = m_settings.rho; ss.eps_prim = m_settings.eps_prim;
+        ss.eps_dual = m_settings.eps_dual; ss.max_iter = m_settings.max_iter; ss.line_search_max_iter = m_settings.line_search_max_iter;
+        ss.regularisation = m_settings.regularisation; ss.exact_hessian_every_iter = m_settings.exact_hessian_every_iter ? 1 : 0;
+        ss.preconditioner = m_settings.preconditioner; ss.hessian_update = m_settings.hessian_update; ss.qp_solver = m_settings.qp_solver;
+        ss.kkt_form = m_settings.kkt_form;
+        m_trace.clear(); m_trace_capacity = 0;
+        const std::vector<double> mp = problem.model_params();
+        std::vector<double> xo(m_x.size()), lo(m_lam.size());
+        const pmpc_status st = pmpc_sqp_solve_batch_prioritised(ctx, device_binding<OCP>::model_id, OCP::POLY_ORDER, OCP::NUM_SEGMENTS, problem.t_start,
+                                                                problem.t_stop, mp.empty() ? nullptr : mp.data(), (int)mp.size(), B, m_x.data(), m_lam.data(),
+                                                                m_p.data(), m_lbx.data(), m_ubx.data(), (NUM_INEQ > 0) ? m_lbg.data() : nullptr,
+                                                                (NUM_INEQ > 0) ? m_ubg.data() : nullptr, &ss, &m_qp_settings, xo.data(), lo.data(),
+                                                                m_info.data(), priority.data());
+        if (st == PMPC_OK) { m_x.swap(xo); m_lam.swap(lo); }
+        return last_error() = st;
+    }
     // the same solve with the batch in contiguous shards [k B / N, (k+1) B / N) over the N contexts of set_devices(), one host thread per shard
     pmpc_status solve_sharded() noexcept {
         // per-instance device state of ONE context cannot follow the shards: no iteration records, and the filter line search runs with a
@@ -678,6 +705,14 @@ public:
     }
     void final_state_bounds(int b, const Vector<nx>& lb, const Vector<nx>& ub) noexcept { for (int i = 0; i < nx; ++i) { lbx(b)[i] = lb(i); ubx(b)[i] = ub(i); } }
     void set_static_parameters(int b, const Vector<nd>& p) noexcept { for (int i = 0; i < nd; ++i) m_p[(size_t)b * (nd > 0 ? nd : 1) + i] = p(i); }
+    // Longest-first dispatch (pmpc_mpc_batch_set_dispatch): step() starts the controllers whose previous step needed the most work first, by
+    // iter_weight * iter + qp_solver_iter of that step; the controls and solutions are those of index order, bit for bit. Off (index order) by
+    // default. While it is on, a step with settings().line_search == 1 is refused: the carried LSFilter is addressed by position.
+    static constexpr int default_iter_weight = 28;   // measured: EXPERIMENTS.md, "longest-first dispatch" (0, 28 and 64 are within each other's spread)
+    pmpc_status dispatch_longest_first(bool on, int iter_weight = default_iter_weight) noexcept {
+        m_dispatch_mode = on ? 1 : 0; m_iter_weight = iter_weight;
+        return m_batch ? (last_error() = pmpc_mpc_batch_set_dispatch(m_batch, m_dispatch_mode, m_iter_weight)) : PMPC_OK;
+    }
     // initial_conditions(x0) + solve() + solution_u_at(t_start) for every controller: x0 holds B*nx states, u0 receives B*nu controls
     pmpc_status step(const double* x0, double* u0) noexcept {
         pmpc_context* ctx = context();
@@ -688,6 +723,7 @@ public:
                                                          mp.empty() ? nullptr : mp.data(), (int)mp.size(), B, m_p.data(), m_lbx.data(), m_ubx.data(),
                                                          num_ineq > 0 ? m_lbg.data() : nullptr, num_ineq > 0 ? m_ubg.data() : nullptr, nullptr, nullptr, &m_batch);
             if (st != PMPC_OK) return last_error() = st;
+            if (m_dispatch_mode != 0) { const pmpc_status ds = pmpc_mpc_batch_set_dispatch(m_batch, m_dispatch_mode, m_iter_weight); if (ds != PMPC_OK) return last_error() = ds; }
         }
         pmpc_sqp_settings ss;
         pmpc_sqp_settings_default(&ss);
@@ -713,6 +749,7 @@ private:
     std::vector<pmpc_sqp_info> m_info;
     sqp_settings_t m_settings; qp_solver_settings_t m_qp_settings;
     pmpc_mpc_batch* m_batch{nullptr};
+    int m_dispatch_mode{0}, m_iter_weight{default_iter_weight};
 public:
     LSFilterHandle filter;   // the solvers' LSFilter members (used when settings().line_search == 1)
 };
@@ -721,6 +758,7 @@ public:
 // device bindings
 #define POLYMPC_USE_BUILTIN_OCP(Name, MODEL_ID)                                                                                       \
     template <> struct polympc::device_binding<Name> {                                                                                \
+        static constexpr int model_id = MODEL_ID;                                                                                     \
         static pmpc_status solve(pmpc_context* ctx, const Name& ocp, int P, int S, double t0, double tf, int B, const double* xg,     \
                                  const double* lg, const double* d, const double* lbx, const double* ubx, const double* lbg,          \
                                  const double* ubg, const pmpc_sqp_settings* ss, const pmpc_qp_settings* qs, double* x, double* lam,  \

@@ -370,6 +370,54 @@ pmpc_status pmpc_mpc_batch_step(pmpc_mpc_batch* batch, const double* x0, const p
 pmpc_status pmpc_mpc_batch_solution(pmpc_mpc_batch* batch, double* x, double* lam);
 pmpc_status pmpc_mpc_batch_destroy(pmpc_mpc_batch* batch);
 
+/* ---- longest-first dispatch -------------------------------------------------------------------------------------------
+ * One launch solves a batch with one wavefront per instance, and workgroups start in index order: an instance that needs many iterations and
+ * starts late ends alone, with the rest of the device idle. A host that has a predictor of an instance's work — a receding-horizon loop has the
+ * counts of its previous step — gives a PRIORITY per instance, and the entry points below solve the batch with the instances of highest priority
+ * at the lowest positions. The solver kernels are the plain calls' own: the per-instance inputs are gathered into dispatch order in staging
+ * buffers of the context, the plain launcher runs on the staged batch, and x / lam / info are scattered back, so inputs stay untouched, outputs
+ * are in INSTANCE order, every instance's result is bit-identical to the plain call's, and pmpc_sqp_last_route reports the same route. That
+ * workgroups start in index order is how the hardware behaves, not a promise: the priority is a hint and changes no result.
+ * Per-instance device state that the kernels address by position cannot travel with a permuted batch: a non-NULL
+ * pmpc_sqp_settings::filter_state or iteration_trace is refused with PMPC_ERR_INVALID_ARGUMENT before any device call (as
+ * pmpc_sqp_solve_batch_multi refuses them). Built-in OCPs only: user-registered OCPs (pmpc_sqp_solve_batch_user) and generic NLPs
+ * (pmpc_nlp_*) have no prioritised form. These are new entry points; by the rule above they do not change PMPC_ABI_VERSION. */
+
+/* order[p] = the instance dispatched at position p (B ints, device): by descending priority, each priority clamped to [0, 65535] first
+ * (negative values count as 0), equal priorities by ascending instance index. priority: B ints on the device, or NULL for the identity.
+ * order must not overlap priority. Any B >= 1 (B == 0: nothing is done). Asynchronous on the context's stream, no host round trip. */
+pmpc_status pmpc_dispatch_order_dev(pmpc_context* ctx, int B, const int* priority, int* order);
+/* The work of a finished solve as a priority: priority[b] = iter_weight * info[b].iter + info[b].qp_solver_iter (saturating; device pointers,
+ * asynchronous). iter_weight: what one SQP iteration costs beyond its QP iterations, in QP iterations. */
+pmpc_status pmpc_sqp_work_priority_dev(pmpc_context* ctx, int B, const pmpc_sqp_info* info, int iter_weight, int* priority);
+/* pmpc_sqp_solve_batch_dev in dispatch order. priority == NULL: the plain call itself (no staging, no extra launch). Three launches more than the
+ * plain call otherwise (order, gather, scatter) and staging for one copy of the batch's inputs and outputs. */
+pmpc_status pmpc_sqp_solve_batch_prioritised_dev(pmpc_context* ctx, int model, int P, int S, double t0, double tf,
+                                                 const double* mparams, int n_mparams, int B, const double* x_guess,
+                                                 const double* lam_guess, const double* d, const double* lbx, const double* ubx,
+                                                 const double* lbg, const double* ubg, const pmpc_sqp_settings* sqp_settings,
+                                                 const pmpc_qp_settings* qp_settings, double* x, double* lam, pmpc_sqp_info* info,
+                                                 const int* priority);
+/* The same with host buffers (priority: B ints on the host, or NULL). */
+pmpc_status pmpc_sqp_solve_batch_prioritised(pmpc_context* ctx, int model, int P, int S, double t0, double tf,
+                                             const double* mparams, int n_mparams, int B, const double* x_guess,
+                                             const double* lam_guess, const double* d, const double* lbx, const double* ubx,
+                                             const double* lbg, const double* ubg, const pmpc_sqp_settings* sqp_settings,
+                                             const pmpc_qp_settings* qp_settings, double* x, double* lam, pmpc_sqp_info* info,
+                                             const int* priority);
+/* pmpc_mpc_step_batch_dev in dispatch order. priority (B ints, device) is in / out: on entry this step's priorities, on return the work of this
+ * step's solve, iter_weight * iter + qp_solver_iter per instance — ready to be passed to the next step. Zeros give index order, so a loop starts
+ * from a zeroed array. priority == NULL: the plain step. */
+pmpc_status pmpc_mpc_step_batch_prioritised_dev(pmpc_context* ctx, int model, int P, int S, double t0, double tf, const double* mparams,
+                                                int n_mparams, int B, const double* x0, const double* d, double* lbx, double* ubx,
+                                                const double* lbg, const double* ubg, const pmpc_sqp_settings* sqp_settings,
+                                                const pmpc_qp_settings* qp_settings, double* x, double* lam, pmpc_sqp_info* info, double* u0,
+                                                int* priority, int iter_weight);
+/* How pmpc_mpc_batch_step orders its batch: mode 0 (default) index order — the plain step, exactly as without this call; mode 1 longest first by
+ * the counts of the batch's previous step (the batch owns the priority array; before the first step: index order), iter_weight as above. Any
+ * other mode: PMPC_ERR_INVALID_ARGUMENT. In mode 1 a step whose settings carry filter_state or iteration_trace is refused as above. */
+pmpc_status pmpc_mpc_batch_set_dispatch(pmpc_mpc_batch* batch, int mode, int iter_weight);
+
 /* ---- user-defined OCPs ---------------------------------------------------------------------------------------------
  * A user's OCP class (the reference's CRTP class with dynamics_impl / lagrange_term_impl / mayer_term_impl /
  * inequality_constraints_impl, continuous_ocp.hpp:191-288) is compiled for the GPU by hipcc in the user's own

@@ -30,6 +30,8 @@ EXPORTED_SYMBOLS = [
     "pmpc_qp_boxadmm_solve_batch", "pmpc_qp_boxadmm_solve_batch_dev", "pmpc_qp_boxadmm_solve_batch_f32", "pmpc_qp_boxadmm_solve_batch_f32_dev", "pmpc_qp_admm_solve_batch_f32", "pmpc_qp_admm_solve_batch_f32_dev", "pmpc_ocp_dims", "pmpc_ocp_linearise_batch",
     "pmpc_sqp_solve_batch", "pmpc_sqp_solve_batch_dev", "pmpc_sqp_solve_batch_user", "pmpc_sqp_solve_batch_multi",
     "pmpc_mpc_step_batch_dev", "pmpc_mpc_batch_create", "pmpc_mpc_batch_step", "pmpc_mpc_batch_solution", "pmpc_mpc_batch_destroy",
+    "pmpc_dispatch_order_dev", "pmpc_sqp_work_priority_dev", "pmpc_sqp_solve_batch_prioritised", "pmpc_sqp_solve_batch_prioritised_dev",
+    "pmpc_mpc_step_batch_prioritised_dev", "pmpc_mpc_batch_set_dispatch",
     "pmpc_qp_admm_solve_batch", "pmpc_qp_admm_solve_batch_dev", "pmpc_qp_ruiz_compute_batch", "pmpc_qp_ruiz_compute_batch_dev", "pmpc_qp_ruiz_unscale_batch", "pmpc_qp_ruiz_unscale_batch_dev",
     "pmpc_filter_state_create", "pmpc_filter_state_clear", "pmpc_filter_state_download", "pmpc_filter_state_destroy",
     "pmpc_iteration_trace_create", "pmpc_iteration_trace_clear", "pmpc_iteration_trace_download", "pmpc_iteration_trace_destroy",
@@ -243,6 +245,59 @@ def _d(t):
     return C.cast(C.c_void_p(t.data_ptr()), C.POINTER(C.c_double))
 
 
+def _dv(t):
+    """torch CUDA tensor of any dtype -> device pointer"""
+    if t is None:
+        return None
+    assert t.is_cuda and t.is_contiguous()
+    return C.c_void_p(t.data_ptr())
+
+
+class MPCBatch:
+    """pmpc_mpc_batch: host arrays in and out, everything else resident (pmpc_mpc_batch_create / _step / _solution / _set_dispatch / _destroy)."""
+
+    def __init__(self, ctx, model, P, S, t0, tf, B, d, lbx, ubx, lbg=None, ubg=None, x_guess=None, lam_guess=None, mparams=None):
+        self.dims = ocp_dims(model, P, S); self.B = int(B)
+        self._batch = C.c_void_p()
+        keep = [_h(a) for a in (mparams, d, lbx, ubx, lbg, ubg, x_guess, lam_guess)]
+        P_ = C.POINTER(C.c_double)
+        f = lib().pmpc_mpc_batch_create
+        f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, P_, C.c_int, C.c_int] + [P_] * 7 + [C.POINTER(C.c_void_p)]
+        _check_status(f(ctx._ctx, model, P, S, t0, tf, keep[0][1], 0 if keep[0][0] is None else len(keep[0][0]), self.B, *[k[1] for k in keep[1:]],
+                        C.byref(self._batch)))
+
+    def set_dispatch(self, mode, iter_weight=0):
+        """pmpc_mpc_batch_set_dispatch: 0 index order (default), 1 longest first by the previous step's counts"""
+        f = lib().pmpc_mpc_batch_set_dispatch
+        f.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        _check_status(f(self._batch, int(mode), int(iter_weight)))
+
+    def step(self, x0, sqp_settings, qp_settings):
+        """pmpc_mpc_batch_step -> u0 (B, nu), info"""
+        xk, xp = _h(x0)
+        u0 = np.zeros((self.B, self.dims["nu"])); info = np.zeros(self.B, dtype=SQP_INFO_DTYPE)
+        P_ = C.POINTER(C.c_double)
+        f = lib().pmpc_mpc_batch_step
+        f.argtypes = [C.c_void_p, P_, C.POINTER(SQPSettings), C.POINTER(QPSettings), P_, C.c_void_p]
+        _check_status(f(self._batch, xp, C.byref(sqp_settings), C.byref(qp_settings), u0.ctypes.data_as(P_), C.c_void_p(info.ctypes.data)))
+        return u0, info
+
+    def solution(self):
+        """pmpc_mpc_batch_solution -> x (B, n), lam (B, m + n)"""
+        n, m = self.dims["n"], self.dims["m"]
+        x = np.zeros((self.B, n)); lam = np.zeros((self.B, m + n))
+        P_ = C.POINTER(C.c_double)
+        f = lib().pmpc_mpc_batch_solution
+        f.argtypes = [C.c_void_p, P_, P_]
+        _check_status(f(self._batch, x.ctypes.data_as(P_), lam.ctypes.data_as(P_)))
+        return x, lam
+
+    def close(self):
+        if self._batch:
+            lib().pmpc_mpc_batch_destroy(self._batch)
+            self._batch = C.c_void_p()
+
+
 class Context:
     """pmpc_context: one per host thread / GPU."""
 
@@ -446,6 +501,65 @@ class Context:
                      [C.POINTER(SQPSettings), C.POINTER(QPSettings), P_, P_, C.c_void_p, P_]
         _check(f(self._ctx, model, P, S, t0, tf, mp, 0 if mk is None else len(mk), B, _d(x0), _d(d), _d(lbx), _d(ubx), _d(lbg), _d(ubg),
                  C.byref(sqp_settings), C.byref(qp_settings), _d(x), _d(lam), C.c_void_p(info.data_ptr()), _d(u0)))
+
+    # ------------------------------------------------------------------ longest-first dispatch (pmpc_dispatch_order_dev and the prioritised solves)
+    def dispatch_order_dev(self, B, priority, order):
+        """pmpc_dispatch_order_dev on torch int32 CUDA tensors (priority may be None: identity); asynchronous on the context's stream"""
+        f = lib().pmpc_dispatch_order_dev
+        f.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        _check_status(f(self._ctx, int(B), _dv(priority), _dv(order)))
+
+    def sqp_work_priority_dev(self, B, info, iter_weight, priority):
+        """pmpc_sqp_work_priority_dev: priority (int32 tensor) = iter_weight * iter + qp_solver_iter of info (uint8 tensor of B * 48 bytes)"""
+        f = lib().pmpc_sqp_work_priority_dev
+        f.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+        _check_status(f(self._ctx, int(B), _dv(info), int(iter_weight), _dv(priority)))
+
+    def sqp_solve_batch_prioritised(self, model, P, S, t0, tf, B, d, lbx, ubx, priority=None, lbg=None, ubg=None, x_guess=None, lam_guess=None,
+                                    sqp_settings=None, qp_settings=None, mparams=None):
+        """pmpc_sqp_solve_batch_prioritised (host buffers; priority: B ints or None) -> x, lam, info in instance order"""
+        dm = ocp_dims(model, P, S); n, m = dm["n"], dm["m"]
+        ss = sqp_settings or sqp_settings_default(); qs = qp_settings or qp_settings_sqp_default()
+        x = np.zeros((B, n)); lam = np.zeros((B, m + n)); info = np.zeros(B, dtype=SQP_INFO_DTYPE)
+        keep = [_h(a) for a in (mparams, x_guess, lam_guess, d, lbx, ubx, lbg, ubg)]
+        pr = None if priority is None else np.ascontiguousarray(priority, dtype=np.int32)
+        P_ = C.POINTER(C.c_double)
+        f = lib().pmpc_sqp_solve_batch_prioritised
+        f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, P_, C.c_int, C.c_int] + [P_] * 7 + \
+                     [C.POINTER(SQPSettings), C.POINTER(QPSettings), P_, P_, C.c_void_p, C.c_void_p]
+        _check_status(f(self._ctx, model, P, S, t0, tf, keep[0][1], 0 if keep[0][0] is None else len(keep[0][0]), B,
+                        *[k[1] for k in keep[1:]], C.byref(ss), C.byref(qs), x.ctypes.data_as(P_), lam.ctypes.data_as(P_),
+                        C.c_void_p(info.ctypes.data), None if pr is None else C.c_void_p(pr.ctypes.data)))
+        return x, lam, info
+
+    def sqp_solve_batch_prioritised_dev(self, model, P, S, t0, tf, B, d, lbx, ubx, x, lam, info, sqp_settings, qp_settings, priority=None, lbg=None,
+                                        ubg=None, x_guess=None, lam_guess=None, mparams=None):
+        """pmpc_sqp_solve_batch_prioritised_dev on torch CUDA tensors (priority: int32 tensor or None); asynchronous on the context's stream"""
+        mk, mp = _h(mparams)
+        P_ = C.POINTER(C.c_double)
+        f = lib().pmpc_sqp_solve_batch_prioritised_dev
+        f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, P_, C.c_int, C.c_int] + [P_] * 7 + \
+                     [C.POINTER(SQPSettings), C.POINTER(QPSettings), P_, P_, C.c_void_p, C.c_void_p]
+        _check_status(f(self._ctx, model, P, S, t0, tf, mp, 0 if mk is None else len(mk), B, _d(x_guess), _d(lam_guess), _d(d),
+                        _d(lbx), _d(ubx), _d(lbg), _d(ubg), C.byref(sqp_settings), C.byref(qp_settings), _d(x), _d(lam),
+                        C.c_void_p(info.data_ptr()), _dv(priority)))
+
+    def mpc_step_batch_prioritised_dev(self, model, P, S, t0, tf, B, x0, d, lbx, ubx, x, lam, info, sqp_settings, qp_settings, priority, iter_weight,
+                                       u0=None, lbg=None, ubg=None, mparams=None):
+        """pmpc_mpc_step_batch_prioritised_dev on torch CUDA tensors: priority (int32 tensor) is read as this step's priorities and overwritten
+        with iter_weight * iter + qp_solver_iter of this step's solve"""
+        mk, mp = _h(mparams)
+        P_ = C.POINTER(C.c_double)
+        f = lib().pmpc_mpc_step_batch_prioritised_dev
+        f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, P_, C.c_int, C.c_int] + [P_] * 6 + \
+                     [C.POINTER(SQPSettings), C.POINTER(QPSettings), P_, P_, C.c_void_p, P_, C.c_void_p, C.c_int]
+        _check_status(f(self._ctx, model, P, S, t0, tf, mp, 0 if mk is None else len(mk), B, _d(x0), _d(d), _d(lbx), _d(ubx), _d(lbg), _d(ubg),
+                        C.byref(sqp_settings), C.byref(qp_settings), _d(x), _d(lam), C.c_void_p(info.data_ptr()), _d(u0), _dv(priority),
+                        int(iter_weight)))
+
+    def mpc_batch(self, model, P, S, t0, tf, B, d, lbx, ubx, lbg=None, ubg=None, x_guess=None, lam_guess=None, mparams=None):
+        """pmpc_mpc_batch_create: B controllers whose data stay on the device between steps (MPCBatch)"""
+        return MPCBatch(self, model, P, S, t0, tf, B, d, lbx, ubx, lbg, ubg, x_guess, lam_guess, mparams)
 
     # ------------------------------------------------------------------ SQP, device buffers (torch tensors), asynchronous
     # ------------------------------------------------------------------ generic NLPs (pmpc_nlp_*)

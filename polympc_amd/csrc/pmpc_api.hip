@@ -15,6 +15,7 @@
 #include "pmpc_ocp.hpp"
 #include "pmpc_sqp.hpp"
 #include "pmpc_launch.hpp"
+#include "pmpc_dispatch.hpp"
 
 using namespace pmpc;
 
@@ -346,12 +347,13 @@ struct pmpc_mpc_batch {
     pmpc_context* ctx; int model, P, S, B, nx, nu, nd, n, m, mi; double t0, tf; std::vector<double> mparams;
     double *d = nullptr, *lbx = nullptr, *ubx = nullptr, *lbg = nullptr, *ubg = nullptr, *x = nullptr, *lam = nullptr, *x0 = nullptr, *u0 = nullptr;
     pmpc_sqp_info* info = nullptr;
+    int dispatch_mode = 0, iter_weight = 0; int* priority = nullptr; bool stepped = false;   // pmpc_mpc_batch_set_dispatch
 };
 pmpc_status pmpc_mpc_batch_destroy(pmpc_mpc_batch* h) {
     if (!h) return PMPC_ERR_INVALID_ARGUMENT;
     (void)hipSetDevice(h->ctx->device);
     (void)hipStreamSynchronize(h->ctx->stream);
-    for (void* q : {(void*)h->d, (void*)h->lbx, (void*)h->ubx, (void*)h->lbg, (void*)h->ubg, (void*)h->x, (void*)h->lam, (void*)h->x0, (void*)h->u0, (void*)h->info})
+    for (void* q : {(void*)h->d, (void*)h->lbx, (void*)h->ubx, (void*)h->lbg, (void*)h->ubg, (void*)h->x, (void*)h->lam, (void*)h->x0, (void*)h->u0, (void*)h->info, (void*)h->priority})
         if (q) (void)hipFree(q);
     delete h;
     return PMPC_OK;
@@ -387,9 +389,14 @@ pmpc_status pmpc_mpc_batch_step(pmpc_mpc_batch* h, const double* x0, const pmpc_
     pmpc_context* ctx = h->ctx;
     HIPCHK(hipSetDevice(ctx->device));
     HIPCHK(hipMemcpyAsync(h->x0, x0, (size_t)h->B * h->nx * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    pmpc_status st = pmpc_mpc_step_batch_dev(ctx, h->model, h->P, h->S, h->t0, h->tf, h->mparams.empty() ? nullptr : h->mparams.data(), (int)h->mparams.size(),
-                                             h->B, h->x0, h->d, h->lbx, h->ubx, h->lbg, h->ubg, ss, qs, h->x, h->lam, h->info, h->u0);
+    const double* mp = h->mparams.empty() ? nullptr : h->mparams.data();
+    pmpc_status st = h->dispatch_mode == 1
+        ? pmpc_mpc_step_batch_prioritised_dev(ctx, h->model, h->P, h->S, h->t0, h->tf, mp, (int)h->mparams.size(), h->B, h->x0, h->d, h->lbx, h->ubx, h->lbg,
+                                              h->ubg, ss, qs, h->x, h->lam, h->info, h->u0, h->priority, h->iter_weight)
+        : pmpc_mpc_step_batch_dev(ctx, h->model, h->P, h->S, h->t0, h->tf, mp, (int)h->mparams.size(), h->B, h->x0, h->d, h->lbx, h->ubx, h->lbg, h->ubg,
+                                  ss, qs, h->x, h->lam, h->info, h->u0);
     if (st != PMPC_OK) return st;
+    h->stepped = true;
     if (u0) HIPCHK(hipMemcpyAsync(u0, h->u0, (size_t)h->B * h->nu * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     if (info) HIPCHK(hipMemcpyAsync(info, h->info, (size_t)h->B * sizeof(pmpc_sqp_info), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -414,6 +421,135 @@ pmpc_status pmpc_sqp_solve_batch(pmpc_context* ctx, int model, int P, int S, dou
     return sqp_solve_host(ctx, B, n, me + mi, nd, mi, {x_guess, lam_guess, d, lbx, ubx, lbg, ubg, x, lam, info}, [&](const SqpBuffers& v) {
         return pmpc_sqp_solve_batch_dev(ctx, model, P, S, t0, tf, mparams, n_mparams, B, v.x_guess, v.lam_guess, v.d, v.lbx, v.ubx, v.lbg, v.ubg, ss, qs, v.x, v.lam, v.info);
     });
+}
+
+/* ---- longest-first dispatch: the plain launcher on a batch gathered into dispatch order (pmpc_dispatch.hpp) ---- */
+static_assert(sizeof(pmpc_sqp_info) == 6 * sizeof(unsigned long long), "pmpc_sqp_info travels as six 64-bit words");
+
+pmpc_status pmpc_dispatch_order_dev(pmpc_context* ctx, int B, const int* priority, int* order) {
+    if (!ctx || B < 0 || !order) return PMPC_ERR_INVALID_ARGUMENT;
+    if (B == 0) return PMPC_OK;
+    HIPCHK(hipSetDevice(ctx->device));
+    Staging stg(ctx);
+    int* tmp = priority ? stg.out<int>(SLOT_DISP_TMP, (size_t)B) : nullptr;
+    if (!stg.ok()) return stg.status;
+    return pmpc_internal_dispatch_order(ctx, B, priority, order, tmp);
+}
+
+pmpc_status pmpc_sqp_work_priority_dev(pmpc_context* ctx, int B, const pmpc_sqp_info* info, int iter_weight, int* priority) {
+    if (!ctx || B < 0 || !info || !priority) return PMPC_ERR_INVALID_ARGUMENT;
+    if (B == 0) return PMPC_OK;
+    HIPCHK(hipSetDevice(ctx->device));
+    return pmpc_internal_dispatch_work(ctx, B, info, iter_weight, priority);
+}
+
+// per-instance device state that the kernels address by position cannot travel with a permuted batch
+static bool has_positional_state(const pmpc_sqp_settings* ss) { return ss->filter_state || ss->iteration_trace; }
+
+// what the MPC step adds to the scatter: u(t_start) from the staged x, and the work of this solve as the next step's priority
+struct MpcScatter { double* u0; int nu, u_off; int* priority; int iter_weight; };
+
+// Validated arguments, B >= 1, priority non-null. The input blocks that exist (non-null, non-empty) are gathered; the others reach the launcher as given.
+static pmpc_status solve_in_dispatch_order(pmpc_context* ctx, int model, int P, int S, double t0, double tf, const double* mparams, int n_mparams, int B,
+                                           int n, int m, int nd, int mi, const double* x_guess, const double* lam_guess, const double* d,
+                                           const double* lbx, const double* ubx, const double* lbg, const double* ubg, const pmpc_sqp_settings* ss,
+                                           const pmpc_qp_settings* qs, double* x, double* lam, pmpc_sqp_info* info, const int* priority,
+                                           const MpcScatter* mpc) {
+    HIPCHK(hipSetDevice(ctx->device));
+    Staging stg(ctx);
+    const size_t Bz = (size_t)B;
+    int *order = stg.out<int>(SLOT_DISP_ORDER, Bz), *tmp = stg.out<int>(SLOT_DISP_TMP, Bz);
+    auto staged = [&](int slot, const double* src, int len) { return src && len > 0 ? stg.out<double>(slot, Bz * len) : nullptr; };
+    double *sxg = staged(SLOT_DISP_XG, x_guess, n), *slg = staged(SLOT_DISP_LG, lam_guess, m + n), *sd = staged(SLOT_DISP_D, d, nd);
+    double *slbx = staged(SLOT_DISP_LBX, lbx, n), *subx = staged(SLOT_DISP_UBX, ubx, n);
+    double *slbg = staged(SLOT_DISP_LBG, lbg, mi), *subg = staged(SLOT_DISP_UBG, ubg, mi);
+    double *sx = stg.out<double>(SLOT_DISP_X, Bz * n), *slam = stg.out<double>(SLOT_DISP_LAM, Bz * (m + n));
+    pmpc_sqp_info* sinfo = stg.out<pmpc_sqp_info>(SLOT_DISP_INFO, Bz);
+    if (!stg.ok()) return stg.status;
+    pmpc_status st = pmpc_internal_dispatch_order(ctx, B, priority, order, tmp);
+    if (st != PMPC_OK) return st;
+    DispatchBlocks in;
+    in.add(x_guess, sxg, n); in.add(lam_guess, slg, m + n); in.add(d, sd, nd); in.add(lbx, slbx, n); in.add(ubx, subx, n); in.add(lbg, slbg, mi); in.add(ubg, subg, mi);
+    st = pmpc_internal_dispatch_gather(ctx, B, order, &in);
+    if (st != PMPC_OK) return st;
+    st = pmpc_sqp_solve_batch_dev(ctx, model, P, S, t0, tf, mparams, n_mparams, B, sxg, slg, sd ? sd : d, slbx, subx, slbg ? slbg : lbg, subg ? subg : ubg,
+                                  ss, qs, sx, slam, sinfo);
+    if (st != PMPC_OK) return st;
+    DispatchBlocks out;
+    out.add(sx, x, n); out.add(slam, lam, m + n); out.add(sinfo, info, (int)(sizeof(pmpc_sqp_info) / sizeof(unsigned long long)));
+    if (mpc && mpc->u0) out.add(sx, mpc->u0, mpc->nu, n, mpc->u_off);
+    return pmpc_internal_dispatch_scatter(ctx, B, order, &out, sinfo, mpc ? mpc->iter_weight : 0, mpc ? mpc->priority : nullptr);
+}
+
+pmpc_status pmpc_sqp_solve_batch_prioritised_dev(pmpc_context* ctx, int model, int P, int S, double t0, double tf, const double* mparams,
+                                                 int n_mparams, int B, const double* x_guess, const double* lam_guess, const double* d,
+                                                 const double* lbx, const double* ubx, const double* lbg, const double* ubg,
+                                                 const pmpc_sqp_settings* ss, const pmpc_qp_settings* qs, double* x, double* lam,
+                                                 pmpc_sqp_info* info, const int* priority) {
+    int nd, n, me, mi;
+    const pmpc_status chk = check_sqp_args(false, ctx, model, P, S, B, d, lbx, ubx, ss, qs, x, lam, info, &nd, &n, &me, &mi);
+    if (chk != PMPC_OK) return chk;
+    if (has_positional_state(ss)) return PMPC_ERR_INVALID_ARGUMENT;
+    if (B == 0) return PMPC_OK;
+    if (!priority) return pmpc_sqp_solve_batch_dev(ctx, model, P, S, t0, tf, mparams, n_mparams, B, x_guess, lam_guess, d, lbx, ubx, lbg, ubg, ss, qs, x, lam, info);
+    return solve_in_dispatch_order(ctx, model, P, S, t0, tf, mparams, n_mparams, B, n, me + mi, nd, mi, x_guess, lam_guess, d, lbx, ubx, lbg, ubg, ss, qs,
+                                   x, lam, info, priority, nullptr);
+}
+
+pmpc_status pmpc_sqp_solve_batch_prioritised(pmpc_context* ctx, int model, int P, int S, double t0, double tf, const double* mparams,
+                                             int n_mparams, int B, const double* x_guess, const double* lam_guess, const double* d,
+                                             const double* lbx, const double* ubx, const double* lbg, const double* ubg,
+                                             const pmpc_sqp_settings* ss, const pmpc_qp_settings* qs, double* x, double* lam, pmpc_sqp_info* info,
+                                             const int* priority) {
+    int nd, n, me, mi;
+    const pmpc_status chk = check_sqp_args(true, ctx, model, P, S, B, d, lbx, ubx, ss, qs, x, lam, info, &nd, &n, &me, &mi);
+    if (chk != PMPC_OK) return chk;
+    if (has_positional_state(ss)) return PMPC_ERR_INVALID_ARGUMENT;
+    if (B == 0) return PMPC_OK;
+    return sqp_solve_host(ctx, B, n, me + mi, nd, mi, {x_guess, lam_guess, d, lbx, ubx, lbg, ubg, x, lam, info}, [&](const SqpBuffers& v) {
+        Staging sp(ctx);
+        const int* dp = sp.in(SLOT_DISP_PRIO, priority, (size_t)B);
+        if (!sp.ok()) return sp.status;
+        return pmpc_sqp_solve_batch_prioritised_dev(ctx, model, P, S, t0, tf, mparams, n_mparams, B, v.x_guess, v.lam_guess, v.d, v.lbx, v.ubx, v.lbg, v.ubg,
+                                                    ss, qs, v.x, v.lam, v.info, dp);
+    });
+}
+
+pmpc_status pmpc_mpc_step_batch_prioritised_dev(pmpc_context* ctx, int model, int P, int S, double t0, double tf, const double* mparams, int n_mparams,
+                                                int B, const double* x0, const double* d, double* lbx, double* ubx, const double* lbg,
+                                                const double* ubg, const pmpc_sqp_settings* ss, const pmpc_qp_settings* qs, double* x, double* lam,
+                                                pmpc_sqp_info* info, double* u0, int* priority, int iter_weight) {
+    if (!x0) return PMPC_ERR_INVALID_ARGUMENT;
+    const pmpc_status chk = check_sqp_args(false, ctx, model, P, S, B, d, lbx, ubx, ss, qs, x, lam, info);
+    if (chk != PMPC_OK) return chk;
+    if (has_positional_state(ss)) return PMPC_ERR_INVALID_ARGUMENT;
+    if (B == 0) return PMPC_OK;
+    if (!priority) return pmpc_mpc_step_batch_dev(ctx, model, P, S, t0, tf, mparams, n_mparams, B, x0, d, lbx, ubx, lbg, ubg, ss, qs, x, lam, info, u0);
+    int nx, nu, np, nd, ng, n, me, mi;
+    const pmpc_status ds = pmpc_ocp_dims(model, P, S, &nx, &nu, &np, &nd, &ng, &n, &me, &mi);
+    if (ds != PMPC_OK) return ds;
+    HIPCHK(hipSetDevice(ctx->device));
+    const int nn = P * S + 1, varx = nx * nn;
+    hipLaunchKernelGGL(mpc_pin_initial_state_kernel, dim3((B * nx + 255) / 256), dim3(256), 0, ctx->stream, B, n, varx, nx, x0, lbx, ubx);
+    HIPCHK(hipGetLastError());
+    // warm start from the current x / lam: the gather into dispatch order is the copy that keeps guess and result apart
+    const MpcScatter mpc{u0, nu, varx + (nn - 1) * nu, priority, iter_weight};
+    return solve_in_dispatch_order(ctx, model, P, S, t0, tf, mparams, n_mparams, B, n, me + mi, nd, mi, x, lam, d, lbx, ubx, lbg, ubg, ss, qs, x, lam, info,
+                                   priority, &mpc);
+}
+
+pmpc_status pmpc_mpc_batch_set_dispatch(pmpc_mpc_batch* h, int mode, int iter_weight) {
+    if (!h || (mode != 0 && mode != 1)) return PMPC_ERR_INVALID_ARGUMENT;
+    if (mode == 1) {
+        pmpc_context* ctx = h->ctx;
+        HIPCHK(hipSetDevice(ctx->device));
+        if (!h->priority) HIPCHK(hipMalloc((void**)&h->priority, (size_t)h->B * sizeof(int)));
+        // the counts of the last step, whatever order it ran in, are the first priorities; before any step: zeros, which is index order
+        if (h->stepped) { const pmpc_status st = pmpc_internal_dispatch_work(ctx, h->B, h->info, iter_weight, h->priority); if (st != PMPC_OK) return st; }
+        else HIPCHK(hipMemsetAsync(h->priority, 0, (size_t)h->B * sizeof(int), ctx->stream));
+    }
+    h->dispatch_mode = mode; h->iter_weight = iter_weight;
+    return PMPC_OK;
 }
 
 /* contiguous shards over n_ctx contexts, one PERSISTENT host thread per context (started on the context's first sharded call, joined

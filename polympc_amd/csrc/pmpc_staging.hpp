@@ -12,11 +12,17 @@
 //   * Reserved for _dev functions, which may run underneath a host wrapper and so must stay clear of its range: SLOT_RUIZ_WORK
 //     (pmpc_qp_ruiz_compute_batch_dev, under 0 .. 9). pmpc_mpc_step_batch_dev keeps its guess copies in SLOT_SQP_XG / SLOT_SQP_LG: it is
 //     called on device buffers only (pmpc_mpc_batch_step), never underneath a wrapper of the SQP range.
-//   * 22 is free.
+//   * The prioritised _dev functions (pmpc_sqp_solve_batch_prioritised_dev, pmpc_mpc_step_batch_prioritised_dev, pmpc_dispatch_order_dev) hold
+//     SLOT_DISP_XG .. SLOT_DISP_TMP, the QP range under names of their own: they run underneath the SQP-shaped host wrapper
+//     (pmpc_sqp_solve_batch_prioritised, SQP range) and above the plain SQP launcher, which takes no slot; no QP-shaped wrapper runs an SQP
+//     underneath. The prioritised MPC step gathers x / lam straight into SLOT_DISP_XG / SLOT_DISP_LG, so SLOT_SQP_XG / SLOT_SQP_LG stay untouched there.
+//     SLOT_DISP_PRIO (22) is the host wrapper's priority upload, live together with the SQP range and the dispatch range.
 enum pmpc_slot : int {
     SLOT_QP_H = 0, SLOT_QP_G, SLOT_QP_A, SLOT_QP_ALB, SLOT_QP_AUB, SLOT_QP_XLB, SLOT_QP_XUB, SLOT_QP_X0, SLOT_QP_Y0, SLOT_QP_X, SLOT_QP_Y, SLOT_QP_INFO,
     SLOT_SQP_XG = 12, SLOT_SQP_LG, SLOT_SQP_D, SLOT_SQP_LBX, SLOT_SQP_UBX, SLOT_SQP_LBG, SLOT_SQP_UBG, SLOT_SQP_X, SLOT_SQP_LAM, SLOT_SQP_INFO,
-    SLOT_RUIZ_WORK = 23, SLOT_COUNT = 24,
+    SLOT_DISP_PRIO = 22, SLOT_RUIZ_WORK = 23, SLOT_COUNT = 24,
+    SLOT_DISP_XG = 0, SLOT_DISP_LG, SLOT_DISP_D, SLOT_DISP_LBX, SLOT_DISP_UBX, SLOT_DISP_LBG, SLOT_DISP_UBG, SLOT_DISP_X, SLOT_DISP_LAM, SLOT_DISP_INFO,
+    SLOT_DISP_ORDER, SLOT_DISP_TMP,   // (the dispatch order and the order kernel's intermediate sequence, B ints each)
     SLOT_RUIZ_D = 7, SLOT_RUIZ_E, SLOT_RUIZ_C, SLOT_UNSCALE_D = 0, SLOT_UNSCALE_E, SLOT_UNSCALE_C, SLOT_UNSCALE_X, SLOT_UNSCALE_Y,
     SLOT_LIN_X = 0, SLOT_LIN_IN1, SLOT_LIN_IN2,   // (the point, then the wrapper's two optional inputs in its own order)
     SLOT_LIN_COST, SLOT_LIN_CONSTR, SLOT_LIN_JAC, SLOT_LIN_COST_GRAD, SLOT_LIN_LAG_GRAD, SLOT_LIN_LAG_HESS,
