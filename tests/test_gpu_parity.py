@@ -551,32 +551,65 @@ def test_mpc_receding_horizon_device_resident(ctx, oracle):
 
 
 # -------------------------------------------------------------------------------------------- A12-A15: fused SQP
-def _sqp_both(ctx, oracle, wl, B, **kw):
+def _sqp_order(oracle, wl, kw):
+    """The restatement order of the kernel that serves workload `wl` under the SQP settings `kw`."""
+    kf = kw.get("kkt_form", 0)
+    dm = oracle.ocp_dims(wl["model"], wl["P"], wl["S"])
+    # (preconditioner = 1, qp_solver = 1 and line_search = 1 are served by the LDS-resident QP kernels whatever the size: static LDL^T
+    #  order; hessian_update = 1 has register-resident specialisations like the default)
+    # (regularisation = 1, eigenvalue mirroring: the hook builds of the register kernels since round 6 — the same routing as the other two hooks)
+    if kw.get("qp_solver", 0): return oracle.PIVOT_STATIC
+    if kw.get("preconditioner", 0) or kw.get("line_search", 0) or kw.get("regularisation", 0) == 1:
+        return _policy_order(oracle, dm["n"], dm["m"], wl["P"] * wl["S"] + 1, ruiz=bool(kw.get("preconditioner", 0)), block_bfgs=bool(kw.get("hessian_update", 0)), kkt_form=kf, ng=dm["ng"])
+    return _gpu_order(oracle, dm["n"], dm["m"], wl["P"] * wl["S"] + 1, block_bfgs=bool(kw.get("hessian_update", 0)), kkt_form=kf, ng=dm["ng"],
+                      schur=_schur_route(wl["model"], wl["P"], wl["S"], **kw))
+
+
+def _sqp_gpu(ctx, wl, B, qp=None, trace=False, **kw):
+    """One fused SQP solve of workload `wl` under its own settings overlaid with `kw` (and the SQP-default QP settings with `qp`).
+    trace: record the iterations, capacity = max_iter -> (x, lam, info[, trace])"""
     import polympc_amd as pa
+    from qp_settings_variants import overlay
     ss = pa.sqp_settings_default(); ss.max_iter = wl["max_iter"]; ss.line_search_max_iter = wl["ls_max_iter"]
     for k, v in kw.items():
         setattr(ss, k, v)
     for k, v in wl.get("settings", {}).items():   # (settings of the workload itself, e.g. the minimal-time problem's exact Hessians + Gershgorin shift)
         if k not in kw: setattr(ss, k, v)
+    qs = None if qp is None else overlay(pa.qp_settings_sqp_default(), qp)
     gk = {k: wl[k] for k in ("x_guess", "lbg", "ubg") if k in wl}
-    x, lam, info = ctx.sqp_solve_batch(wl["model"], wl["P"], wl["S"], wl["t0"], wl["tf"], B, wl["d"], wl["lbx"], wl["ubx"], sqp_settings=ss, **gk)
+    args = (wl["model"], wl["P"], wl["S"], wl["t0"], wl["tf"], B, wl["d"], wl["lbx"], wl["ubx"])
+    if not trace:
+        return ctx.sqp_solve_batch(*args, sqp_settings=ss, qp_settings=qs, **gk)
+    h = ctx.iteration_trace_create(B, ss.max_iter)
+    try:
+        ss.iteration_trace = h; ss.iteration_trace_capacity = ss.max_iter
+        return ctx.sqp_solve_batch(*args, sqp_settings=ss, qp_settings=qs, **gk) + (ctx.iteration_trace_download(B, ss.max_iter, h),)
+    finally:
+        ctx.iteration_trace_destroy(h)
+
+
+def _sqp_oracle(oracle, wl, B, qp=None, trace=False, **kw):
+    """The CPU restatement of _sqp_gpu's solve, in the order of the kernel that serves it -> (x, lam, info[, trace])"""
+    from qp_settings_variants import overlay
     oss = oracle.sqp_default_settings(); oss.max_iter = wl["max_iter"]; oss.line_search_max_iter = wl["ls_max_iter"]
     for k, v in wl.get("settings", {}).items():
         if k not in kw: setattr(oss, k, v)
     for k, v in kw.items():
         if k != "kkt_form": setattr(oss, k, v)   # (how the large-instance kernel arranges its linear algebra: a pivot policy on the CPU side)
-    kf = kw.get("kkt_form", 0)
-    n = wl["lbx"].shape[1]; dm = oracle.ocp_dims(wl["model"], wl["P"], wl["S"])
-    # (preconditioner = 1, qp_solver = 1 and line_search = 1 are served by the LDS-resident QP kernels whatever the size: static LDL^T
-    #  order; hessian_update = 1 has register-resident specialisations like the default)
-    # (regularisation = 1, eigenvalue mirroring: the hook builds of the register kernels since round 6 — the same routing as the other two hooks)
-    if kw.get("qp_solver", 0): order = oracle.PIVOT_STATIC
-    elif kw.get("preconditioner", 0) or kw.get("line_search", 0) or kw.get("regularisation", 0) == 1: order = _policy_order(oracle, dm["n"], dm["m"], wl["P"] * wl["S"] + 1, ruiz=bool(kw.get("preconditioner", 0)), block_bfgs=bool(kw.get("hessian_update", 0)), kkt_form=kf, ng=dm["ng"])
-    else: order = _gpu_order(oracle, dm["n"], dm["m"], wl["P"] * wl["S"] + 1, block_bfgs=bool(kw.get("hessian_update", 0)), kkt_form=kf, ng=dm["ng"],
-                             schur=_schur_route(wl["model"], wl["P"], wl["S"], **kw))
-    xo, lo, io = oracle.sqp_solve_batch(wl["model"], wl["P"], wl["S"], wl["t0"], wl["tf"], B, wl["d"], wl["lbx"], wl["ubx"],
-                                        sqp_settings=oss, pivot=order, threads=8, **gk)
-    return (x, lam, info), (xo, lo, io)
+    oqs = None if qp is None else overlay(oracle.sqp_qp_default_settings(), qp)
+    gk = {k: wl[k] for k in ("x_guess", "lbg", "ubg") if k in wl}
+    otr = None
+    if trace:
+        otr = np.zeros((B, oss.max_iter, oracle.TRACE_DOUBLES)); oracle.bind_iteration_trace(oss, otr)
+    res = oracle.sqp_solve_batch(wl["model"], wl["P"], wl["S"], wl["t0"], wl["tf"], B, wl["d"], wl["lbx"], wl["ubx"],
+                                 sqp_settings=oss, qp_settings=oqs, pivot=_sqp_order(oracle, wl, kw), threads=8, **gk)
+    return res + (otr,) if trace else res
+
+
+def _sqp_both(ctx, oracle, wl, B, qp=None, trace=False, **kw):
+    """The GPU solve and its restatement. qp: a variant overlaid on the SQP-default QP settings of both sides (qp_settings_variants.overlay);
+    trace: both sides record their iterations (capacity max_iter), returned as a fourth element."""
+    return _sqp_gpu(ctx, wl, B, qp=qp, trace=trace, **kw), _sqp_oracle(oracle, wl, B, qp=qp, trace=trace, **kw)
 
 
 def test_sqp_config_A_vs_oracle(ctx, oracle):

@@ -6,8 +6,6 @@ iteration cap, other rho / alpha / sigma / tolerances. Prints one line per combi
 import os
 import sys
 
-import numpy as np
-
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, ".."))
 sys.path.insert(0, HERE)
@@ -25,19 +23,9 @@ def main():
     cases = [("cstr 11", workloads.cstr_batch(B)), ("robot 16", workloads.robot_batch(B, P=5, S=3)), ("robot 11", workloads.robot_batch(B, P=5, S=2)),
              ("robot 13", workloads.robot_batch(B, P=6, S=2))]
     for name, wl in cases:
-        dm = ob.ocp_dims(wl["model"], wl["P"], wl["S"])
         for kkt_form in (0, 1):
             for kw in VARIANTS:
-                ss = pa.sqp_settings_default(); oss = ob.sqp_default_settings()
-                for st in (ss, oss):
-                    st.max_iter = 5; st.line_search_max_iter = wl["ls_max_iter"]; st.kkt_form = kkt_form
-                qs = pa.qp_settings_sqp_default(); oqs = ob.sqp_qp_default_settings()
-                for k, v in kw.items():
-                    setattr(qs, k, v); setattr(oqs, k, v)
-                x, lam, info = ctx.sqp_solve_batch(wl["model"], wl["P"], wl["S"], wl["t0"], wl["tf"], B, wl["d"], wl["lbx"], wl["ubx"], sqp_settings=ss, qp_settings=qs)
-                order = T._gpu_order(ob, dm["n"], dm["m"], wl["P"] * wl["S"] + 1, kkt_form=kkt_form, ng=dm["ng"])
-                xo, lo, io = ob.sqp_solve_batch(wl["model"], wl["P"], wl["S"], wl["t0"], wl["tf"], B, wl["d"], wl["lbx"], wl["ubx"], sqp_settings=oss, qp_settings=oqs,
-                                                pivot=order, threads=8)
+                (x, lam, info), (xo, lo, io) = T._sqp_both(ctx, ob, wl, B, qp=kw, max_iter=5, kkt_form=kkt_form)   # (the helper of tests/test_gpu_sqp_settings.py: QP variant overlaid on both sides, the serving kernel's order)
                 try:
                     T._assert_same_solve(info, io, x, xo, lam, lo)
                     res = "ok"
