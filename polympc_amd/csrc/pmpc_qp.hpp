@@ -63,6 +63,44 @@ __device__ __forceinline__ double wave_max(double v) {
     const int hi = __builtin_amdgcn_readlane(__double2hiint(v), 63);
     return __hiloint2double(hi, lo);
 }
+// a <-> b exchanges: swap32 trades a's lanes 32..63 with b's lanes 0..31, swap16 a's odd 16-lane rows with b's even rows
+__device__ __forceinline__ void swap32(double& a, double& b) {
+    const auto lo = __builtin_amdgcn_permlane32_swap(__double2loint(a), __double2loint(b), false, false);
+    const auto hi = __builtin_amdgcn_permlane32_swap(__double2hiint(a), __double2hiint(b), false, false);
+    a = __hiloint2double(hi[0], lo[0]); b = __hiloint2double(hi[1], lo[1]);
+}
+__device__ __forceinline__ void swap16(double& a, double& b) {
+    const auto lo = __builtin_amdgcn_permlane16_swap(__double2loint(a), __double2loint(b), false, false);
+    const auto hi = __builtin_amdgcn_permlane16_swap(__double2hiint(a), __double2hiint(b), false, false);
+    a = __hiloint2double(hi[0], lo[0]); b = __hiloint2double(hi[1], lo[1]);
+}
+// Five wave maxima in ONE transposed reduction: a .. e <- their maxima over the 64 lanes, on every lane. For NON-NEGATIVE per-lane values (norms): max is
+// exact and order-free, fmax drops a NaN in any order and there is no -0 among them, so any tree gives the bits of five wave_max calls. While a quantity
+// still spans more lanes than the exchange distance two quantities share a register — each exchange halves the lanes a quantity needs:
+//   half-waves (swap32):   [a | b], [c | d], [e | e]           5 -> 3 registers   (lanes 0..31 | 32..63)
+//   16-lane rows (swap16): [a, c, b, d], [e, e, e, e]          3 -> 2             (rows 0, 1, 2, 3)
+//   8 lanes (row_ror:8):   every row [its quantity | e]        2 -> 1             (lanes 0..7 | 8..15 of the row: the one lane-dependent select)
+// then three steps inside the 8-lane groups on the one register and five broadcasts from fixed lanes: 9 exchange steps where five wave_max take 30.
+// `lane`: this lane's id (bit 3 is all that is used). Every exchange is a builtin, so the compiler's hazard recogniser places the two wait states between
+// a fresh VALU result and its DPP / permlane read.
+__device__ __forceinline__ void wave_max5(double& a, double& b, double& c, double& d, double& e, unsigned lane) {
+    double e2 = e;
+    swap32(a, b); swap32(c, d); swap32(e, e2);
+    double p = fmax(a, b), q = fmax(c, d), t = fmax(e, e2);
+    double t2 = t;
+    swap16(p, q); swap16(t, t2);
+    const double s = fmax(p, q); t = fmax(t, t2);
+    const bool up = (lane & 8u) != 0;                 // selects, never a branch (compiler hazard 3)
+    const double keep = up ? t : s, give = up ? s : t;
+    const int glo = __builtin_amdgcn_update_dpp(__double2loint(give), __double2loint(give), 0x128, 0xf, 0xf, false);   // row_ror:8
+    const int ghi = __builtin_amdgcn_update_dpp(__double2hiint(give), __double2hiint(give), 0x128, 0xf, 0xf, false);
+    double u = fmax(keep, __hiloint2double(ghi, glo));
+    u = dpp_max_step<0xB1, 0xf>(u);    // quad_perm [1,0,3,2]
+    u = dpp_max_step<0x4E, 0xf>(u);    // quad_perm [2,3,0,1]
+    u = dpp_max_step<0x141, 0xf>(u);   // row_half_mirror: every lane of an 8-lane group holds the group's maximum
+    auto from = [&](int l) { return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(u), l), __builtin_amdgcn_readlane(__double2loint(u), l)); };
+    a = from(0); c = from(16); b = from(32); d = from(48); e = from(8);
+}
 // sum over the 64 lanes, returned to every lane, through the same six DPP steps: the partial sums are added PAIRWISE OVER ADJACENT LANES, level by
 // level (lanes 2i and 2i+1, then quads, half rows, rows, row pairs, the two halves) — a fixed balanced tree, which the CPU restatement of the callers
 // walks (every addition is commutative, so which side a partner arrives on does not matter). Rows that a step's row mask leaves out add +0.

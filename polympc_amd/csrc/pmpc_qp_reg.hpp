@@ -90,17 +90,7 @@ __device__ __forceinline__ double fmac_rowbcast(double acc, double x, double w) 
     asm("v_fmac_f64_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf" : "+v"(acc) : "v"(x), "v"(w), "i"(J));
     return acc;
 }
-// a <-> b exchanges: swap32 trades a's lanes 32..63 with b's lanes 0..31, swap16 a's odd 16-lane rows with b's even rows
-__device__ __forceinline__ void swap32(double& a, double& b) {
-    const auto lo = __builtin_amdgcn_permlane32_swap(__double2loint(a), __double2loint(b), false, false);
-    const auto hi = __builtin_amdgcn_permlane32_swap(__double2hiint(a), __double2hiint(b), false, false);
-    a = __hiloint2double(hi[0], lo[0]); b = __hiloint2double(hi[1], lo[1]);
-}
-__device__ __forceinline__ void swap16(double& a, double& b) {
-    const auto lo = __builtin_amdgcn_permlane16_swap(__double2loint(a), __double2loint(b), false, false);
-    const auto hi = __builtin_amdgcn_permlane16_swap(__double2hiint(a), __double2hiint(b), false, false);
-    a = __hiloint2double(hi[0], lo[0]); b = __hiloint2double(hi[1], lo[1]);
-}
+// (the a <-> b exchanges swap32 / swap16 of apply() live in pmpc_qp.hpp, next to the wave reductions that use them too)
 
 // the lane id re-materialised next to a batch of loads (two v_mbcnt tied to the opaque zero `zo`): a long-lived per-lane offset is spilled, and its
 // scratch reload in the middle of the batch waits on vmcnt for every load issued before it
@@ -109,6 +99,40 @@ __device__ __forceinline__ unsigned lane_id_near(int zo) {
     asm("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=&v"(l) : "v"(zo));
     return l;
 }
+
+// RESIDUAL TRIM (boxadmm_solve_reg, residuals_update): fewer issue slots per residual evaluation, not one bit of any residual changed. Developer switch for
+// the A/B of its stages (profiles/*_ab_residual_trim.txt): 0 five wave_max and an address computed in front of every load; 1 the five norms in one
+// transposed reduction (wave_max5); 2 on the stacked workspace also the addresses of an evaluation from two per-lane offsets computed once
+// (StackedResidualAddr).
+#ifndef PMPC_RESIDUAL_TRIM
+#define PMPC_RESIDUAL_TRIM 2
+#endif
+// The byte offsets of one evaluation's loads into the stacked (NN + MM) x NN column-major workspace [H; A] (uniform base ws): row `lane` is read at NN
+// columns 8 N bytes apart, column `lane` of A at MM consecutive doubles. Every load is  global_load  ws (scalar pair) + offset (one VGPR) + immediate; the
+// immediate is 13 bits signed, so a row base sits in the middle of every W = 2 SPAN + 1 columns and reaches SPAN columns to either side (35 + 21: two bases
+// for the 35 columns). Built INSIDE the evaluation from a lane id re-materialised behind its opaque zero `zo`, like the per-load form it replaces: defined
+// outside, the offsets are hoisted out of the ADMM loop, stay live across apply() and spill. Lanes past the last row / column read row / column 0.
+template <int NN, int MM>
+struct StackedResidualAddr {
+    static constexpr int N = NN + MM;
+    static constexpr int SPAN = 4095 / (N * 8), W = 2 * SPAN + 1, NG = (NN + W - 1) / W;
+    unsigned row[NG], col;
+    __device__ __forceinline__ StackedResidualAddr(unsigned l, int zo) {
+        const unsigned r0 = ((l < (unsigned)N ? l : 0u) << 3) + (unsigned)zo;
+#pragma unroll
+        for (int g = 0; g < NG; ++g) { unsigned b = r0 + (unsigned)((g * W + SPAN) * N * 8); asm("" : "+v"(b)); row[g] = b; }
+        unsigned c = ((l < (unsigned)NN ? l : 0u) * (unsigned)(N * 8) + (unsigned)(NN * 8)) + (unsigned)zo;
+        asm("" : "+v"(c));
+        col = c;
+    }
+    __device__ __forceinline__ double krow(const double* ws, int j) const {   // ws(lane, j), j < NN
+        const int g = j / W;
+        return *(const double*)((const char*)ws + row[g] + (j - (g * W + SPAN)) * (N * 8));
+    }
+    __device__ __forceinline__ double acol(const double* ws, int k) const {   // A(k, lane) = ws(NN + k, lane), k < MM
+        return *(const double*)((const char*)ws + col + k * 8);
+    }
+};
 
 // DIRECT TILE STAGING (RegKkt::invert, constraint-first mode): the KKT tiles and the operands of the rank-m update are loaded from the stacked
 // [H; A] workspace straight in MFMA layout, instead of row-per-lane and transposed through LDS. Developer switch for the A/B of its stages
@@ -653,6 +677,11 @@ __device__ __forceinline__ void boxadmm_solve_reg(const double* __restrict__ H, 
         else return colA[k + zo];
     };
     constexpr int LDH = STACKED ? N : NN;
+    // PMPC_RESIDUAL_TRIM >= 2, stacked workspace: the residual evaluations (and the z = A x_guess product) take their addresses from the two per-lane offsets of
+    // StackedResidualAddr, built once per evaluation. The per-lane base and stride of the QP entry kernels already share ONE stride + opaque-zero term among
+    // the loads of an evaluation (their columns are a 64-bit multiply-add away, there is no immediate to reach them by), and the staging loaders of invert()
+    // (kcol: Krow, KrowLower, Acol, called load by load from inside RegKkt::invert) keep the per-load form.
+    constexpr bool TRIM_ADDR = STACKED && PMPC_RESIDUAL_TRIM >= 2;
 
     // state: xv = x (primal lanes) / z (constraint lanes); yv = y_box / y_a; qv = q (primal lanes)
     double xv = 0.0, yv = 0.0, qv = 0.0;
@@ -662,8 +691,14 @@ __device__ __forceinline__ void boxadmm_solve_reg(const double* __restrict__ H, 
     }
     if (x0) {  // z = A * x_guess
         double acc = 0.0;
+        if constexpr (TRIM_ADDR) {
+            const StackedResidualAddr<NN, MM> ad(lane_id_near(0), 0);
 #pragma unroll
-        for (int j = 0; j < NN; ++j) acc += Krow(j, 0) * bcast_lane(xv, j);
+            for (int j = 0; j < NN; ++j) acc += ad.krow(H, j) * bcast_lane(xv, j);
+        } else {
+#pragma unroll
+            for (int j = 0; j < NN; ++j) acc += Krow(j, 0) * bcast_lane(xv, j);
+        }
         xv = isC ? acc : xv;
     }
 
@@ -752,13 +787,16 @@ __device__ __forceinline__ void boxadmm_solve_reg(const double* __restrict__ H, 
                 asm volatile("" : "+v"(zr));
                 double acc = 0.0;      // lanes < n: (H x)_i ; lanes in [n, N): (A x)_r
                 double aty = 0.0;      // lanes < n: (A^T y_a)_i
+                const unsigned lnear = PMPC_RESIDUAL_TRIM >= 1 ? lane_id_near(zr) : 0u;   // one re-materialised lane id per evaluation (addresses, the packed reduction)
+                const StackedResidualAddr<NN, MM> ad(lnear, zr);                         // (dead unless TRIM_ADDR)
 #pragma unroll
                 for (int e0 = 0; e0 < N; e0 += RC) {
                     double mv[RC];
 #pragma unroll
                     for (int e = 0; e < RC; ++e) {
                         const int ee = e0 + e;
-                        mv[e] = (ee < NN) ? Krow(ee < NN ? ee : 0, zr) : ((ee < N) ? Acol((ee >= NN && ee < N) ? ee - NN : 0, zr) : 0.0);
+                        if constexpr (TRIM_ADDR) mv[e] = (ee < NN) ? ad.krow(H, ee < NN ? ee : 0) : ((ee < N) ? ad.acol(H, (ee >= NN && ee < N) ? ee - NN : 0) : 0.0);
+                        else mv[e] = (ee < NN) ? Krow(ee < NN ? ee : 0, zr) : ((ee < N) ? Acol((ee >= NN && ee < N) ? ee - NN : 0, zr) : 0.0);
                     }
 #pragma unroll
                     for (int e = 0; e < RC; ++e) {
@@ -772,11 +810,17 @@ __device__ __forceinline__ void boxadmm_solve_reg(const double* __restrict__ H, 
                 //   max(|Ax|, |z|, |x|):  constraint lanes carry |(Ax)_r| and |z_r|, primal lanes |x_i|
                 //   max(|Hx|, |A'y|, |h|, |y_box|):  primal lanes only (hv is zero elsewhere)
                 const double ax = fabs(xv);
-                max_Ax_z_norm = wave_max(isC ? fmax(fabs(acc), ax) : (isP ? ax : 0.0));
-                max_Hx_ATy_h_norm = wave_max(isP ? fmax(fmax(fabs(acc), fabs(aty)), fmax(fabs(hv), fabs(yv))) : 0.0);
-                const double rp = wave_max(isC ? fabs(acc - xv) : 0.0), rq = wave_max(isP ? fabs(xv - qv) : 0.0);
+                double nA = isC ? fmax(fabs(acc), ax) : (isP ? ax : 0.0);
+                double nH = isP ? fmax(fmax(fabs(acc), fabs(aty)), fmax(fabs(hv), fabs(yv))) : 0.0;
+                double rp = isC ? fabs(acc - xv) : 0.0, rq = isP ? fabs(xv - qv) : 0.0;
+                double rd = isP ? fabs(((acc + hv) + aty) + yv) : 0.0;
+                // five maxima of absolute values: one transposed reduction (9 exchange steps) instead of five six-step ones
+                if constexpr (PMPC_RESIDUAL_TRIM >= 1) wave_max5(nA, nH, rp, rq, rd, lnear);
+                else { nA = wave_max(nA); nH = wave_max(nH); rp = wave_max(rp); rq = wave_max(rq); rd = wave_max(rd); }
+                max_Ax_z_norm = nA;
+                max_Hx_ATy_h_norm = nH;
                 res_prim = rp + rq;
-                res_dual = wave_max(isP ? fabs(((acc + hv) + aty) + yv) : 0.0);
+                res_dual = rd;
                 if (dbg) dbg[1] += clock64() - r0;
             }
             if (check) {
