@@ -214,6 +214,7 @@ __global__ __launch_bounds__(WG4 ? 256 : 64, ((NN > 0 && NN + MM <= 64) ? PMPC_S
         const size_t have = (size_t)(stage_end - ocp.s.fval);   // the staging block only — never the parameters / filter carved behind it
         sqp.lsbuf = ocp.s.fval;   // a flag, not a null pointer, says whether it fits (compiler hazard 7: null tests of LDS pointers)
         sqp.ls_side_by_side = (G >= 2 && need <= have);
+        sqp.ls_wide = sqp.ls_side_by_side && need + (size_t)2 * G * n <= have;   // the box-term pairs of the G candidates behind them (PMPC_WIDE_TERMS >= 2; without room the summing lanes form the terms)
     }
     pmpc_sqp_info si;
     sqp.qp_flags = flags0;
@@ -304,6 +305,7 @@ void sqp_schur_kernel(Model model, const ChebData* __restrict__ cd, int B, const
         const size_t have = (size_t)(stage_end - ocp.s.fval);
         sqp.lsbuf = ocp.s.fval;
         sqp.ls_side_by_side = (G >= 2 && need <= have);
+        sqp.ls_wide = sqp.ls_side_by_side && need + (size_t)2 * G * n <= have;
     }
     pmpc_sqp_info si;
     sqp.solve(si, 0, ss.max_iter);

@@ -25,7 +25,37 @@
 #define PMPC_EXPERIMENT_FORCE_SYMLOWER 0   /* 1: developer experiment (round 6, EXPERIMENTS.md) — the headline kernel's KKT build reads the LOWER triangle of H only (one address select per load): what any
                                               half / packed storage of the BFGS matrix would cost on the read side */
 #endif
+// WIDE TERMS (the phases of the fused loop in which few lanes worked): the same operations on the same operands, formed where the lanes are. Developer switch for
+// the A/B of its stages (profiles/*_ab_wide_terms.txt): 0 one row of B per lane in the rank-2 update, one lane per candidate for every term of the line search's
+// sums; 1 the rank-2 update of the dense damped BFGS on the lower triangle, dealt over all 64 lanes (TriDeal, bfgs_update_tri); 2 also the box terms of the line
+// search formed in its node phase, from the registers that hold x + alpha p there (step_size_selection, `wide`).
+#ifndef PMPC_WIDE_TERMS
+#define PMPC_WIDE_TERMS 2
+#endif
 namespace pmpc {
+
+// The lower triangle of an n x n matrix dealt over the wavefront: entry t = lane + 64 e (slot e = 0 .. SLOTS-1) of the T = n (n + 1) / 2 entries (i, j), i >= j.
+// Rows q and n-1-q hold q + 1 and n - q entries, n + 1 together; they are folded into rectangle q of W = n + 1 columns (n odd: the middle row (n-1)/2 is its own
+// partner and fills the first half of the last rectangle, which is where T ends):
+//     R = t / W, c = t - R W;    c <= R: (i, j) = (R, c)    else: (i, j) = (n - 1 - R, c - R - 1)
+// Every (i, j), i >= j, is hit by exactly one t < T. t >= T (the tail of the last slot) is CLAMPED to T - 1: those lanes repeat the last entry, the same bits to
+// the same address — no lane is switched off. The quotient is a multiply and a shift (MAGIC; checked for every t below).
+template <int N_>
+struct TriDeal {
+    static constexpr int T = N_ * (N_ + 1) / 2, W = N_ + 1, SLOTS = (T + WAVE - 1) / WAVE;
+    static constexpr unsigned MAGIC = (65536u + W - 1) / W;
+    static constexpr bool magic_ok() { for (unsigned t = 0; t < (unsigned)T; ++t) if (((t * MAGIC) >> 16) != t / (unsigned)W) return false; return true; }
+    static_assert(magic_ok(), "TriDeal: t / (n + 1) by multiply and shift");
+    static constexpr bool slot_full(int e) { return WAVE * e + WAVE - 1 < T; }
+    __device__ __forceinline__ static void entry(unsigned lane, int e, unsigned& i, unsigned& j) {
+        unsigned t = lane + (unsigned)(WAVE * e);
+        if (!slot_full(e)) t = t < (unsigned)T ? t : (unsigned)(T - 1);
+        const unsigned R = (t * MAGIC) >> 16, c = t - R * (unsigned)W;
+        const bool low = c <= R;
+        i = low ? R : (unsigned)(N_ - 1) - R;
+        j = low ? c : c - R - 1u;
+    }
+};
 
 struct SqpLds {
     double *x, *lam, *lam_k, *h, *lg, *lgn, *al, *au, *lx, *ux, *lbx, *ubx, *lbg, *ubg, *step, *xs, *cb, *t1, *t2, *t3;
@@ -89,6 +119,7 @@ struct SqpDevice {
     QpLds& qw;
     double* lsbuf = nullptr;   // LDS scratch of the side-by-side line search (aliases the MFMA staging, free outside the QP)
     bool ls_side_by_side = false;   // lsbuf holds G >= 2 candidates
+    bool ls_wide = false;           // ... and behind them the two box terms of every variable of every candidate (PMPC_WIDE_TERMS >= 2)
     bool cb_valid = false;     // v.cb holds the constraint values of the CURRENT iterate (set by the line search)
     double* tr = nullptr;  // LDS transpose scratch of the register-resident QP (aliases the per-node AD staging, dead during the QP)
     double* Hw;  // H(i,j) = Hw[j*ldw + i]  — upper block of the stacked (n+m) x n HBM workspace [H ; J]
@@ -245,6 +276,13 @@ struct SqpDevice {
         double* cand_viol = cand_L + G * NNo;      // [G]
         double* cand_cost = cand_viol + G;         // [G]
         double* cand_alpha = cand_cost + G;        // [G]
+        // WIDE: the box terms fmax(lbx - xi, 0), fmax(xi - ubx, 0) of every variable of every candidate are formed in the node phase, by the lane of (candidate,
+        // node) that holds xi = x + alpha p of its node's states and inputs in registers anyway (the NN nodes of a candidate hold each of its n variables once; the
+        // parameters are node 0's), and left in LDS as pairs; the candidate's summing lane reads the pairs and runs the same two ordered chains, idx ascending.
+        // Without room for the pairs (the launcher's flag) the summing lane forms the terms itself, as before.
+        constexpr bool WIDE_CT = PMPC_WIDE_TERMS >= 2 && NN > 0;
+        const bool wide = WIDE_CT && ls_wide;
+        double* cand_box = cand_alpha + G;         // [G][n][2]   (wide only)
         const long long p0_ = now();
         const double mu = lds_inf_norm(v.lam_k, m + n);
         const double gp = seq_dot(v.h, p, n);
@@ -279,6 +317,14 @@ struct SqpDevice {
                 for (int q = 0; q < NX; ++q) { xk[q] = xat(k * NX + q); f[q] = 0.0; }
                 for (int q = 0; q < NU; ++q) uk[q] = xat(VARX + k * NU + q);
                 for (int q = 0; q < NP; ++q) pk[q] = xat(VARX + VARU + q);
+                if constexpr (WIDE_CT) {
+                    if (wide) {
+                        auto box = [&](int idx, double xi) { double* o = cand_box + 2 * (g * n + idx); o[0] = fmax(v.lbx[idx] - xi, 0.0); o[1] = fmax(xi - v.ubx[idx], 0.0); };
+                        for (int q = 0; q < NX; ++q) box(k * NX + q, xk[q]);
+                        for (int q = 0; q < NU; ++q) box(VARX + k * NU + q, uk[q]);
+                        if (NP > 0 && k == 0) for (int q = 0; q < NP; ++q) box(VARX + VARU + q, pk[q]);
+                    }
+                }
                 const double tk = ocp.s.tn[k];
                 ocp.model.template dynamics_impl<Value>(as_cvalues(xk), as_cvalues(uk), as_cvalues(pk), cref<double>(ocp.d), Value(tk), as_values(f));
                 int seg, row; ocp.seg_row(k, seg, row);
@@ -349,6 +395,15 @@ struct SqpDevice {
                 }
                 cl1 += slo; cl1 += shi;
                 slo = 0.0; shi = 0.0;
+                if (wide) {
+                    for (int i0 = 0; i0 < n_; i0 += CH) {
+                        double lo[CH], hi[CH];
+#pragma unroll
+                        for (int i = 0; i < CH; ++i) { const int ii = (i0 + i < n_) ? i0 + i : 0; lo[i] = cand_box[2 * (gc * n_ + ii)]; hi[i] = cand_box[2 * (gc * n_ + ii) + 1]; }
+#pragma unroll
+                        for (int i = 0; i < CH; ++i) if (i0 + i < n_) { slo += lo[i]; shi += hi[i]; }
+                    }
+                } else
                 for (int i0 = 0; i0 < n_; i0 += CH) {
                     double pv[CH], xv[CH], lb[CH], ub[CH];
 #pragma unroll
@@ -696,6 +751,7 @@ struct SqpDevice {
             const long long b0 = now();
             if constexpr (SCH) bfgs_update_block();
             else if constexpr (REG1 && HU == 1) bfgs_update_block();
+            else if constexpr (TRI_BFGS) bfgs_update_tri();
             else if constexpr (REG1) { double brow[NN > 0 ? NN : 1]; bfgs_load_row(brow); bfgs_update_reg(brow); }
             else if constexpr (REG2) { if (__builtin_amdgcn_readfirstlane(ss.hessian_update) == 1) bfgs_update_block(); else bfgs_update_reg2(); }
             else { if (__builtin_amdgcn_readfirstlane(ss.hessian_update) == 1) bfgs_update_block(); else bfgs_update(); }   // (the launcher routes hessian_update = 1 to these kernels)
@@ -853,6 +909,63 @@ struct SqpDevice {
             const unsigned io = (unsigned)i + opaque_zero();
 #pragma unroll
             for (int j = 0; j < NN; ++j) (Hw + (size_t)(j * (NN + MM)))[io] = brow[j];
+        }
+        wfence();
+        wsync();
+    }
+    // The same update with its rank-2 part on the LOWER TRIANGLE, dealt over all 64 lanes (PMPC_WIDE_TERMS >= 1): for the one-row-per-lane kernels with the dense
+    // damped BFGS and a BITWISE SYMMETRIC B (the precondition of the direct tile staging, pmpc_qp_reg.hpp: no block BFGS, no hook build). Row i on lane i formed all
+    // n entries of its row — n of 64 lanes at work, and every off-diagonal entry formed twice, (-Bs_i Bs_j and r_i r_j commute: the update keeps B symmetric bit for bit).
+    // Here the n (n + 1) / 2 entries (i, j), i >= j, are dealt TriDeal::SLOTS per lane (10 at n = 35): loaded beside the row loads, updated by the expression of
+    // bfgs_update_reg, stored to (i, j) and to (j, i) — storage stays full, the KKT staging and the residual evaluations read rows and columns as before.
+    // Unchanged: the row loads and B s (lane i, columns ascending), the scalar products, the damping, the early return and the generic-division fallback.
+    // No lane is switched off in the new part (clamped entries, TriDeal): nothing here narrows EXEC over live registers.
+    static constexpr bool TRI_BFGS = PMPC_WIDE_TERMS >= 1 && REG1 && HU == 0 && !POL;
+    __device__ __forceinline__ void bfgs_update_tri() {
+        using TD = TriDeal<(NN > 0 ? NN : 1)>;
+        constexpr unsigned LDW = NN + MM;
+        const int ln = lane_id();
+        const int i = ln < NN ? ln : 0;
+        double* Bs = v.t1; double* r = v.t2; double* y = v.t3;
+        double brow[NN > 0 ? NN : 1], bent[TD::SLOTS];
+        bfgs_load_row(brow);
+        {
+            const unsigned zo = opaque_zero();
+#pragma unroll
+            for (int e = 0; e < TD::SLOTS; ++e) { unsigned ei, ej; TD::entry((unsigned)ln, e, ei, ej); bent[e] = Hw[ej * LDW + ei + zo]; }
+        }
+        {
+            double a = 0.0;
+#pragma unroll
+            for (int j = 0; j < NN; ++j) a += brow[j] * v.step[j];
+            if (ln < NN) { Bs[i] = a; y[i] = v.lgn[i] - v.lg[i]; }
+        }
+        wsync();
+        double sBs, sy;
+        seq_dot_pair(v.step, Bs, y, sBs, sy);
+        double sr;
+        if (sy < 0.2 * sBs) {
+            const double theta = 0.8 * sBs / (sBs - sy);
+            if (ln < NN) r[i] = theta * y[i] + (1 - theta) * Bs[i];
+            sr = theta * sy + (1 - theta) * sBs;
+        } else {
+            if (ln < NN) r[i] = y[i];
+            sr = sy;
+        }
+        wsync();
+        if (__builtin_amdgcn_readfirstlane((int)(sr < DBL_EPS))) return;
+        const UniformDiv by_sBs(sBs), by_sr(sr);   // the same quotients as "/ sBs", "/ sr", bit for bit
+        if (!(by_sBs.ok() && by_sr.ok())) { rank2_update_mem(Bs, r, sBs, sr); return; }   // divisor outside the window of UniformDiv: generic divisions, in place in the workspace (rare)
+        const unsigned zo = opaque_zero();
+#pragma unroll
+        for (int e = 0; e < TD::SLOTS; ++e) {
+            unsigned ei, ej; TD::entry((unsigned)ln, e, ei, ej);
+            const double Bsi = Bs[ei], Bsj = Bs[ej], ri = r[ei], rj = r[ej];
+            double b = bent[e];
+            b += by_sBs(-Bsi * Bsj);
+            b += by_sr(ri * rj);
+            Hw[ej * LDW + ei + zo] = b;
+            Hw[ei * LDW + ej + zo] = b;
         }
         wfence();
         wsync();
