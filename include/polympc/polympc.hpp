@@ -741,6 +741,24 @@ public:
         x.resize((size_t)B * var_size);
         return last_error() = pmpc_mpc_batch_solution(m_batch, x.data(), nullptr);
     }
+    // MPC::solution_x_at(t) / solution_u_at(t) (mpc_wrapper.hpp:245-281) of every controller, interpolated on the device from the resident
+    // iterate (pmpc_mpc_batch_sample): out receives B * nx states resp. B * nu controls, controller b at out[b * nx ..] resp. out[b * nu ..]
+    pmpc_status solution_x_at(double t, std::vector<double>& out) noexcept {
+        if (!m_batch) return PMPC_ERR_INVALID_ARGUMENT;
+        out.resize((size_t)B * nx);
+        return last_error() = pmpc_mpc_batch_sample(m_batch, 1, &t, 0, out.data(), nullptr);
+    }
+    pmpc_status solution_u_at(double t, std::vector<double>& out) noexcept {
+        if (!m_batch) return PMPC_ERR_INVALID_ARGUMENT;
+        out.resize((size_t)B * nu);
+        return last_error() = pmpc_mpc_batch_sample(m_batch, 1, &t, 0, nullptr, out.data());
+    }
+    // The time-shifted warm start (pmpc_mpc_batch_shift): every controller's iterate — with `duals` also its multipliers — is moved forward by
+    // dt along the horizon, in HBM; the next step() starts from it. step() never shifts by itself. The horizon must start at 0.
+    pmpc_status shift(double dt, bool duals = false) noexcept {
+        if (!m_batch) return PMPC_ERR_INVALID_ARGUMENT;
+        return last_error() = pmpc_mpc_batch_shift(m_batch, dt, duals ? 1 : 0);
+    }
 private:
     double* lbx(int b) noexcept { return &m_lbx[(size_t)b * var_size]; }
     double* ubx(int b) noexcept { return &m_ubx[(size_t)b * var_size]; }

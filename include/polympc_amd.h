@@ -418,6 +418,46 @@ pmpc_status pmpc_mpc_step_batch_prioritised_dev(pmpc_context* ctx, int model, in
  * other mode: PMPC_ERR_INVALID_ARGUMENT. In mode 1 a step whose settings carry filter_state or iteration_trace is refused as above. */
 pmpc_status pmpc_mpc_batch_set_dispatch(pmpc_mpc_batch* batch, int mode, int iter_weight);
 
+/* ---- trajectories on the device: x(t) / u(t), time-shifted warm start, change of grid ---------------------------------------
+ * MPC::solution_x_at(t) / solution_u_at(t) (mpc_wrapper.hpp:245-281) for a batch whose iterates stay in HBM. All three entries evaluate the
+ * piecewise Lagrange interpolant of an iterate's per-node blocks, with L = (tf - t0) / S and s_j the forward nodes of the first segment:
+ *   idx = clamp((int)floor(t / L), 0, S - 1);  tl = t - idx * L              (t is taken as is: times outside the horizon are served by the
+ *   l_i = 1; for j = 0..P, j != i: l_i = l_i * ((tl - s_j) / (s_i - s_j))     polynomial of the first / last segment)
+ *   r   = 0; for i = 0..P:         r   = r + l_i * v_{idx P + i}             (v_k: value at the k-th node counted forward in time)
+ * — MPC<OCP>::interpolate of the C++ mirror, operation for operation, so a result is the same bits whatever the batch or the launch looks like.
+ * The entries take the OCP's dimensions, not a model id: iterates of user-registered OCPs are served too. x: B * ((nx + nu) * nn + np) in the
+ * OCP variable layout above, nn = P * S + 1. P <= 15, nn <= 64 (PMPC_ERR_UNSUPPORTED_SIZE beyond); nx >= 1, nu, np >= 0; tf > t0. B == 0:
+ * nothing is done. The _dev forms take device pointers and are asynchronous on the context's stream. These are new entry points; they do not
+ * change PMPC_ABI_VERSION. */
+
+/* xs[(b * K + q) * nx + c], us[(b * K + q) * nu + c] = x_c, u_c of instance b at time q. t: K times shared by the batch (t_per_instance = 0) or
+ * B * K times (1). Either output may be NULL, not both. The outputs must not overlap x, t or each other (PMPC_ERR_INVALID_ARGUMENT). Any t0: it
+ * behaves as the mirror does — t / L locates the segment, so only a horizon that starts at 0 is interpolated where its nodes are. */
+pmpc_status pmpc_traj_sample_batch_dev(pmpc_context* ctx, int B, int nx, int nu, int np, int P, int S, double t0, double tf, const double* x, int K,
+                                       const double* t, int t_per_instance, double* xs, double* us);
+/* The same with host buffers. */
+pmpc_status pmpc_traj_sample_batch(pmpc_context* ctx, int B, int nx, int nu, int np, int P, int S, double t0, double tf, const double* x, int K,
+                                   const double* t, int t_per_instance, double* xs, double* us);
+/* The warm start moved forward by dt, IN PLACE: the k-th node (counted forward) of the x and the u block receives the interpolant of the old
+ * iterate at min(t_k + dt, tf); the np parameters stay. lam: NULL, or the B * (m + n) duals — then every per-node block of lam is shifted the same
+ * way: lam_eq (nx per node), lam_ineq (ng per node), lam_box over x (nx) and over u (nu); the np box multipliers of the parameters stay.
+ * dt: finite, >= 0. t0 must be 0 (a receding horizon is solved in relative time; PMPC_ERR_INVALID_ARGUMENT otherwise). The old blocks of an
+ * instance are staged in LDS: PMPC_ERR_UNSUPPORTED_SIZE when they do not fit. */
+pmpc_status pmpc_traj_shift_batch_dev(pmpc_context* ctx, int B, int nx, int nu, int np, int ng, int P, int S, double t0, double tf, double dt,
+                                      double* x, double* lam);
+/* A (P, S) iterate on the (P2, S2) grid of the same horizon (primal only): the k-th node of the new grid receives the interpolant at that
+ * grid's own node time; the np parameters are copied. x_dst: B * ((nx + nu) * (P2 * S2 + 1) + np), must not overlap x_src. t0 must be 0. */
+pmpc_status pmpc_traj_regrid_batch_dev(pmpc_context* ctx, int B, int nx, int nu, int np, int P, int S, int P2, int S2, double t0, double tf,
+                                       const double* x_src, double* x_dst);
+/* The same with host buffers. */
+pmpc_status pmpc_traj_regrid_batch(pmpc_context* ctx, int B, int nx, int nu, int np, int P, int S, int P2, int S2, double t0, double tf,
+                                   const double* x_src, double* x_dst);
+/* On the opaque batch: sample uploads the K (or B * K) times, samples the batch's current iterate and downloads xs (B * K * nx) and / or us
+ * (B * K * nu), host arrays; shift moves the batch's iterate (and, shift_duals != 0, its duals) forward by dt on the context's stream — the next
+ * pmpc_mpc_batch_step then starts from the shifted iterate. A step never shifts by itself. */
+pmpc_status pmpc_mpc_batch_sample(pmpc_mpc_batch* batch, int K, const double* t, int t_per_instance, double* xs, double* us);
+pmpc_status pmpc_mpc_batch_shift(pmpc_mpc_batch* batch, double dt, int shift_duals);
+
 /* ---- user-defined OCPs ---------------------------------------------------------------------------------------------
  * A user's OCP class (the reference's CRTP class with dynamics_impl / lagrange_term_impl / mayer_term_impl /
  * inequality_constraints_impl, continuous_ocp.hpp:191-288) is compiled for the GPU by hipcc in the user's own

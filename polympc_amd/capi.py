@@ -32,6 +32,8 @@ EXPORTED_SYMBOLS = [
     "pmpc_mpc_step_batch_dev", "pmpc_mpc_batch_create", "pmpc_mpc_batch_step", "pmpc_mpc_batch_solution", "pmpc_mpc_batch_destroy",
     "pmpc_dispatch_order_dev", "pmpc_sqp_work_priority_dev", "pmpc_sqp_solve_batch_prioritised", "pmpc_sqp_solve_batch_prioritised_dev",
     "pmpc_mpc_step_batch_prioritised_dev", "pmpc_mpc_batch_set_dispatch",
+    "pmpc_traj_sample_batch", "pmpc_traj_sample_batch_dev", "pmpc_traj_shift_batch_dev", "pmpc_traj_regrid_batch", "pmpc_traj_regrid_batch_dev",
+    "pmpc_mpc_batch_sample", "pmpc_mpc_batch_shift",
     "pmpc_qp_admm_solve_batch", "pmpc_qp_admm_solve_batch_dev", "pmpc_qp_ruiz_compute_batch", "pmpc_qp_ruiz_compute_batch_dev", "pmpc_qp_ruiz_unscale_batch", "pmpc_qp_ruiz_unscale_batch_dev",
     "pmpc_filter_state_create", "pmpc_filter_state_clear", "pmpc_filter_state_download", "pmpc_filter_state_destroy",
     "pmpc_iteration_trace_create", "pmpc_iteration_trace_clear", "pmpc_iteration_trace_download", "pmpc_iteration_trace_destroy",
@@ -291,6 +293,26 @@ class MPCBatch:
         f.argtypes = [C.c_void_p, P_, P_]
         _check_status(f(self._batch, x.ctypes.data_as(P_), lam.ctypes.data_as(P_)))
         return x, lam
+
+    def sample(self, t, per_instance=False, want_x=True, want_u=True):
+        """pmpc_mpc_batch_sample: the batch's current iterate at the times t — K times shared by the batch, or (B, K) with per_instance
+        -> xs (B, K, nx), us (B, K, nu); an output that is not wanted is None"""
+        tk, tp = _h(t)
+        K = tk.shape[-1] if tk.ndim else 1
+        assert tk.size == (self.B * K if per_instance else K)
+        xs = np.zeros((self.B, K, self.dims["nx"])) if want_x else None
+        us = np.zeros((self.B, K, self.dims["nu"])) if want_u else None
+        P_ = C.POINTER(C.c_double)
+        f = lib().pmpc_mpc_batch_sample
+        f.argtypes = [C.c_void_p, C.c_int, P_, C.c_int, P_, P_]
+        _check_status(f(self._batch, int(K), tp, 1 if per_instance else 0, _h(xs)[1], _h(us)[1]))
+        return xs, us
+
+    def shift(self, dt, duals=False):
+        """pmpc_mpc_batch_shift: move the batch's iterate (duals: and its multipliers) forward by dt; the next step starts from it"""
+        f = lib().pmpc_mpc_batch_shift
+        f.argtypes = [C.c_void_p, C.c_double, C.c_int]
+        _check_status(f(self._batch, float(dt), 1 if duals else 0))
 
     def close(self):
         if self._batch:
@@ -556,6 +578,52 @@ class Context:
         _check_status(f(self._ctx, model, P, S, t0, tf, mp, 0 if mk is None else len(mk), B, _d(x0), _d(d), _d(lbx), _d(ubx), _d(lbg), _d(ubg),
                         C.byref(sqp_settings), C.byref(qp_settings), _d(x), _d(lam), C.c_void_p(info.data_ptr()), _d(u0), _dv(priority),
                         int(iter_weight)))
+
+    # ------------------------------------------------------------------ trajectories: x(t) / u(t), shifted warm start, regridding (pmpc_traj_*)
+    _TRAJ_SAMPLE_ARGTYPES = [C.c_void_p] + [C.c_int] * 6 + [C.c_double] * 2 + [C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double), C.c_int] + \
+                            [C.POINTER(C.c_double)] * 2
+    _TRAJ_REGRID_ARGTYPES = [C.c_void_p] + [C.c_int] * 8 + [C.c_double] * 2 + [C.POINTER(C.c_double)] * 2
+
+    def traj_sample_batch(self, nx, nu, np_, P, S, t0, tf, x, t, per_instance=False, want_x=True, want_u=True):
+        """pmpc_traj_sample_batch (host buffers): x (B, n) at the times t — K shared times, or (B, K) with per_instance
+        -> xs (B, K, nx), us (B, K, nu); an output that is not wanted is None"""
+        xk, xp = _h(np.atleast_2d(x)); B = xk.shape[0]
+        tk, tp = _h(t)
+        K = tk.shape[-1] if tk.ndim else 1
+        assert tk.size == (B * K if per_instance else K)
+        xs = np.zeros((B, K, nx)) if want_x else None
+        us = np.zeros((B, K, nu)) if want_u else None
+        f = lib().pmpc_traj_sample_batch
+        f.argtypes = self._TRAJ_SAMPLE_ARGTYPES
+        _check_status(f(self._ctx, B, nx, nu, np_, P, S, t0, tf, xp, int(K), tp, 1 if per_instance else 0, _h(xs)[1], _h(us)[1]))
+        return xs, us
+
+    def traj_sample_batch_dev(self, B, nx, nu, np_, P, S, t0, tf, x, K, t, per_instance, xs=None, us=None):
+        """pmpc_traj_sample_batch_dev on torch CUDA tensors (xs (B, K, nx) and / or us (B, K, nu)); asynchronous on the context's stream"""
+        f = lib().pmpc_traj_sample_batch_dev
+        f.argtypes = self._TRAJ_SAMPLE_ARGTYPES
+        _check_status(f(self._ctx, int(B), nx, nu, np_, P, S, t0, tf, _d(x), int(K), _d(t), 1 if per_instance else 0, _d(xs), _d(us)))
+
+    def traj_shift_batch_dev(self, B, nx, nu, np_, ng, P, S, t0, tf, dt, x, lam=None):
+        """pmpc_traj_shift_batch_dev on torch CUDA tensors, in place (lam: the duals, or None); asynchronous on the context's stream"""
+        f = lib().pmpc_traj_shift_batch_dev
+        f.argtypes = [C.c_void_p] + [C.c_int] * 7 + [C.c_double] * 3 + [C.POINTER(C.c_double)] * 2
+        _check_status(f(self._ctx, int(B), nx, nu, np_, ng, P, S, t0, tf, float(dt), _d(x), _d(lam)))
+
+    def traj_regrid_batch(self, nx, nu, np_, P, S, P2, S2, t0, tf, x):
+        """pmpc_traj_regrid_batch (host buffers): x (B, n) of the (P, S) grid -> (B, n2) on the (P2, S2) grid"""
+        xk, xp = _h(np.atleast_2d(x)); B = xk.shape[0]
+        out = np.zeros((B, (nx + nu) * (P2 * S2 + 1) + np_))
+        f = lib().pmpc_traj_regrid_batch
+        f.argtypes = self._TRAJ_REGRID_ARGTYPES
+        _check_status(f(self._ctx, B, nx, nu, np_, P, S, P2, S2, t0, tf, xp, _h(out)[1]))
+        return out
+
+    def traj_regrid_batch_dev(self, B, nx, nu, np_, P, S, P2, S2, t0, tf, x_src, x_dst):
+        """pmpc_traj_regrid_batch_dev on torch CUDA tensors; asynchronous on the context's stream"""
+        f = lib().pmpc_traj_regrid_batch_dev
+        f.argtypes = self._TRAJ_REGRID_ARGTYPES
+        _check_status(f(self._ctx, int(B), nx, nu, np_, P, S, P2, S2, t0, tf, _d(x_src), _d(x_dst)))
 
     def mpc_batch(self, model, P, S, t0, tf, B, d, lbx, ubx, lbg=None, ubg=None, x_guess=None, lam_guess=None, mparams=None):
         """pmpc_mpc_batch_create: B controllers whose data stay on the device between steps (MPCBatch)"""

@@ -552,6 +552,34 @@ pmpc_status pmpc_mpc_batch_set_dispatch(pmpc_mpc_batch* h, int mode, int iter_we
     return PMPC_OK;
 }
 
+/* ---- x(t) / u(t) and the time-shifted warm start of an opaque batch (the kernels and the pmpc_traj_* entries: pmpc_traj.hip) ---- */
+pmpc_status pmpc_mpc_batch_sample(pmpc_mpc_batch* h, int K, const double* t, int t_per_instance, double* xs, double* us) {
+    if (!h || K < 1 || !t || (!xs && !us) || (t_per_instance != 0 && t_per_instance != 1)) return PMPC_ERR_INVALID_ARGUMENT;
+    pmpc_context* ctx = h->ctx;
+    int np = 0;
+    pmpc_status st = pmpc_ocp_dims(h->model, h->P, h->S, nullptr, nullptr, &np, nullptr, nullptr, nullptr, nullptr, nullptr);
+    if (st != PMPC_OK) return st;
+    HIPCHK(hipSetDevice(ctx->device));
+    Staging stg(ctx);   // (the QP range of the staging slots: nothing else of this context is live during the call)
+    const size_t Bz = (size_t)h->B;
+    const double* dt = stg.in(SLOT_QP_H, t, t_per_instance ? Bz * K : (size_t)K);
+    double* dxs = xs ? stg.out<double>(SLOT_QP_G, Bz * K * h->nx) : nullptr;
+    double* dus = us ? stg.out<double>(SLOT_QP_A, Bz * K * h->nu) : nullptr;
+    if (!stg.ok()) return stg.status;
+    st = pmpc_traj_sample_batch_dev(ctx, h->B, h->nx, h->nu, np, h->P, h->S, h->t0, h->tf, h->x, K, dt, t_per_instance, dxs, dus);
+    if (st != PMPC_OK) return st;
+    if (xs) stg.fetch(xs, dxs, Bz * K * h->nx);
+    if (us) stg.fetch(us, dus, Bz * K * h->nu);
+    return stg.sync();
+}
+pmpc_status pmpc_mpc_batch_shift(pmpc_mpc_batch* h, double dt, int shift_duals) {
+    if (!h || !(dt >= 0.0 && dt <= 1.7976931348623157e308)) return PMPC_ERR_INVALID_ARGUMENT;   // (a bad dt is refused before the handle is read)
+    int np = 0, ng = 0;
+    const pmpc_status st = pmpc_ocp_dims(h->model, h->P, h->S, nullptr, nullptr, &np, nullptr, &ng, nullptr, nullptr, nullptr);
+    if (st != PMPC_OK) return st;
+    return pmpc_traj_shift_batch_dev(h->ctx, h->B, h->nx, h->nu, np, ng, h->P, h->S, h->t0, h->tf, dt, h->x, shift_duals ? h->lam : nullptr);
+}
+
 /* contiguous shards over n_ctx contexts, one PERSISTENT host thread per context (started on the context's first sharded call, joined
    by pmpc_destroy), no collective. The contexts must be distinct objects (two contexts on one device are fine; one context twice is not: its
    stream, workspace and staging buffers serve one call at a time). */
