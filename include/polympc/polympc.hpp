@@ -676,7 +676,8 @@ private:
 
 // ---------------------------------------------------------------------------------------------------------------------
 // BatchMPC<OCP>: B independent MPC<OCP> controllers whose bounds, static parameters and primal / dual iterate stay in HBM between
-// steps (pmpc_mpc_batch_*). Per step only the measured states go up and the controls to apply come down. Built-in OCPs.
+// steps (pmpc_mpc_batch_*). Per step only the measured states go up and the controls to apply come down. The batch is created through
+// device_binding<OCP>::mpc_create, so built-in and registered OCPs are served alike.
 template <typename OCP>
 class BatchMPC {
 public:
@@ -696,7 +697,10 @@ public:
     sqp_settings_t& settings() noexcept { return m_settings; }
     qp_solver_settings_t& qp_settings() noexcept { return m_qp_settings; }
     void set_time_limits(const double& t0, const double& tf) noexcept { problem.set_time_limits(t0, tf); }
-    // the setters of mpc_wrapper.hpp:103-187 for instance b; they are uploaded by the first step()
+    // the setters of mpc_wrapper.hpp:103-187 for instance b; they are uploaded by the first step(), and after it by update()
+    void constraints_bounds(int b, const Vector<OCP::NG>& lb, const Vector<OCP::NG>& ub) noexcept {
+        for (int k = 0; k < num_nodes; ++k) for (int i = 0; i < OCP::NG; ++i) { m_lbg[(size_t)b * num_ineq + k * OCP::NG + i] = lb(i); m_ubg[(size_t)b * num_ineq + k * OCP::NG + i] = ub(i); }
+    }
     void control_bounds(int b, const Vector<nu>& lb, const Vector<nu>& ub) noexcept {
         for (int k = 0; k < num_nodes; ++k) for (int i = 0; i < nu; ++i) { lbx(b)[varx_size + k * nu + i] = lb(i); ubx(b)[varx_size + k * nu + i] = ub(i); }
     }
@@ -718,10 +722,9 @@ public:
         pmpc_context* ctx = context();
         if (!ctx) return last_error();
         if (!m_batch) {
-            const std::vector<double> mp = problem.model_params();
-            const pmpc_status st = pmpc_mpc_batch_create(ctx, device_binding<OCP>::model_id, OCP::POLY_ORDER, OCP::NUM_SEGMENTS, problem.t_start, problem.t_stop,
-                                                         mp.empty() ? nullptr : mp.data(), (int)mp.size(), B, m_p.data(), m_lbx.data(), m_ubx.data(),
-                                                         num_ineq > 0 ? m_lbg.data() : nullptr, num_ineq > 0 ? m_ubg.data() : nullptr, nullptr, nullptr, &m_batch);
+            const pmpc_status st = device_binding<OCP>::mpc_create(ctx, problem, OCP::POLY_ORDER, OCP::NUM_SEGMENTS, problem.t_start, problem.t_stop, B, m_p.data(),
+                                                                   m_lbx.data(), m_ubx.data(), num_ineq > 0 ? m_lbg.data() : nullptr,
+                                                                   num_ineq > 0 ? m_ubg.data() : nullptr, nullptr, nullptr, &m_batch);
             if (st != PMPC_OK) return last_error() = st;
             if (m_dispatch_mode != 0) { const pmpc_status ds = pmpc_mpc_batch_set_dispatch(m_batch, m_dispatch_mode, m_iter_weight); if (ds != PMPC_OK) return last_error() = ds; }
         }
@@ -733,6 +736,14 @@ public:
         ss.hessian_update = m_settings.hessian_update; ss.qp_solver = m_settings.qp_solver;
         { const pmpc_status fs = filter.bind(ctx, B, m_settings.line_search, ss); if (fs != PMPC_OK) return last_error() = fs; }
         return last_error() = pmpc_mpc_batch_step(m_batch, x0, &ss, &m_qp_settings, u0, m_info.data());
+    }
+    // The setters after the first step() (MPC::set_static_parameters and the bound setters are callable at any time, mpc_wrapper.hpp:103-187):
+    // update() uploads what they currently hold (pmpc_mpc_batch_update); the next step() pins its x0 again. Without it a setter called after
+    // the first step() changes nothing on the device.
+    pmpc_status update() noexcept {
+        if (!m_batch) return PMPC_ERR_INVALID_ARGUMENT;
+        return last_error() = pmpc_mpc_batch_update(m_batch, nd > 0 ? m_p.data() : nullptr, m_lbx.data(), m_ubx.data(), num_ineq > 0 ? m_lbg.data() : nullptr,
+                                                    num_ineq > 0 ? m_ubg.data() : nullptr);
     }
     const pmpc_sqp_info& info(int b) const noexcept { return m_info[b]; }
     // current primal solution of every controller (B * var_size), downloaded on demand
@@ -785,6 +796,13 @@ public:
             return pmpc_sqp_solve_batch(ctx, MODEL_ID, P, S, t0, tf, mp.empty() ? nullptr : mp.data(), (int)mp.size(), B, xg, lg, d,  \
                                         lbx, ubx, lbg, ubg, ss, qs, x, lam, info);                                                    \
         }                                                                                                                             \
+        static pmpc_status mpc_create(pmpc_context* ctx, const Name& ocp, int P, int S, double t0, double tf, int B, const double* d, \
+                                      const double* lbx, const double* ubx, const double* lbg, const double* ubg, const double* xg,   \
+                                      const double* lg, pmpc_mpc_batch** batch) {                                                     \
+            const std::vector<double> mp = ocp.model_params();                                                                        \
+            return pmpc_mpc_batch_create(ctx, MODEL_ID, P, S, t0, tf, mp.empty() ? nullptr : mp.data(), (int)mp.size(), B, d, lbx,    \
+                                         ubx, lbg, ubg, xg, lg, batch);                                                               \
+        }                                                                                                                             \
     };
 
 // DeviceModel = the plain struct registered with PMPC_REGISTER_OCP in the .hip translation unit; the host OCP class exposes
@@ -802,6 +820,13 @@ public:
             const auto dm = ocp.device_model();                                                                                       \
             return pmpc_sqp_solve_batch_user(ctx, pmpc_user_sqp_dev_##DeviceModel, &dm, Name::NX, Name::NU, Name::NP, Name::ND,       \
                                              Name::NG, P, S, t0, tf, B, xg, lg, d, lbx, ubx, lbg, ubg, ss, qs, x, lam, info);         \
+        }                                                                                                                             \
+        static pmpc_status mpc_create(pmpc_context* ctx, const Name& ocp, int P, int S, double t0, double tf, int B, const double* d, \
+                                      const double* lbx, const double* ubx, const double* lbg, const double* ubg, const double* xg,   \
+                                      const double* lg, pmpc_mpc_batch** batch) {                                                     \
+            const auto dm = ocp.device_model();   /* the batch keeps its own copy of these bytes */                                   \
+            return pmpc_mpc_batch_create_user(ctx, pmpc_user_sqp_dev_##DeviceModel, &dm, sizeof(DeviceModel), Name::NX, Name::NU,     \
+                                              Name::NP, Name::ND, Name::NG, P, S, t0, tf, B, d, lbx, ubx, lbg, ubg, xg, lg, batch);   \
         }                                                                                                                             \
     };
 
@@ -834,12 +859,18 @@ public:
 };
 }  // namespace models
 template <typename A> struct device_binding<models::MobileRobot<A>> {
-    static constexpr int model_id = PMPC_MODEL_ROBOT;   // built-in device code: usable with BatchMPC
+    static constexpr int model_id = PMPC_MODEL_ROBOT;   // built-in device code: what BatchSolver's prioritised solve asks for
     static pmpc_status solve(pmpc_context* ctx, const models::MobileRobot<A>& ocp, int P, int S, double t0, double tf, int B, const double* xg,
                              const double* lg, const double* d, const double* lbx, const double* ubx, const double* lbg, const double* ubg,
                              const pmpc_sqp_settings* ss, const pmpc_qp_settings* qs, double* x, double* lam, pmpc_sqp_info* info) {
         const std::vector<double> mp = ocp.model_params();
         return pmpc_sqp_solve_batch(ctx, PMPC_MODEL_ROBOT, P, S, t0, tf, mp.data(), (int)mp.size(), B, xg, lg, d, lbx, ubx, lbg, ubg, ss, qs, x, lam, info);
+    }
+    static pmpc_status mpc_create(pmpc_context* ctx, const models::MobileRobot<A>& ocp, int P, int S, double t0, double tf, int B, const double* d,
+                                  const double* lbx, const double* ubx, const double* lbg, const double* ubg, const double* xg, const double* lg,
+                                  pmpc_mpc_batch** batch) {
+        const std::vector<double> mp = ocp.model_params();
+        return pmpc_mpc_batch_create(ctx, PMPC_MODEL_ROBOT, P, S, t0, tf, mp.data(), (int)mp.size(), B, d, lbx, ubx, lbg, ubg, xg, lg, batch);
     }
 };
 template <typename A> struct device_binding<models::CSTR<A>> {
@@ -848,6 +879,10 @@ template <typename A> struct device_binding<models::CSTR<A>> {
                              const double* lg, const double* d, const double* lbx, const double* ubx, const double* lbg, const double* ubg,
                              const pmpc_sqp_settings* ss, const pmpc_qp_settings* qs, double* x, double* lam, pmpc_sqp_info* info) {
         return pmpc_sqp_solve_batch(ctx, PMPC_MODEL_CSTR, P, S, t0, tf, nullptr, 0, B, xg, lg, d, lbx, ubx, lbg, ubg, ss, qs, x, lam, info);
+    }
+    static pmpc_status mpc_create(pmpc_context* ctx, const models::CSTR<A>&, int P, int S, double t0, double tf, int B, const double* d, const double* lbx,
+                                  const double* ubx, const double* lbg, const double* ubg, const double* xg, const double* lg, pmpc_mpc_batch** batch) {
+        return pmpc_mpc_batch_create(ctx, PMPC_MODEL_CSTR, P, S, t0, tf, nullptr, 0, B, d, lbx, ubx, lbg, ubg, xg, lg, batch);
     }
 };
 }  // namespace polympc

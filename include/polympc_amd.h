@@ -360,7 +360,9 @@ pmpc_status pmpc_mpc_step_batch_dev(pmpc_context* ctx, int model, int P, int S, 
 /* The same for callers that hold no device pointers (plain C / C++ hosts): an opaque batch of B controllers that keeps bounds,
  * static parameters, primal / dual iterate and results in HBM between steps. create uploads the problem data once (x_guess /
  * lam_guess may be NULL: zeros); step uploads only x0 (B*NX), runs pmpc_mpc_step_batch_dev and downloads u(t_start) (B*NU) and,
- * if wanted, the per-instance info; solution downloads the current primal / dual iterate (either pointer may be NULL). */
+ * if wanted, the per-instance info; solution downloads the current primal / dual iterate (either pointer may be NULL). Problem data that
+ * change later go up with pmpc_mpc_batch_update; a registered OCP's batch comes from pmpc_mpc_batch_create_user (both below, with the
+ * user-defined OCPs). */
 typedef struct pmpc_mpc_batch pmpc_mpc_batch;
 pmpc_status pmpc_mpc_batch_create(pmpc_context* ctx, int model, int P, int S, double t0, double tf, const double* mparams, int n_mparams,
                                   int B, const double* d, const double* lbx, const double* ubx, const double* lbg, const double* ubg,
@@ -380,8 +382,10 @@ pmpc_status pmpc_mpc_batch_destroy(pmpc_mpc_batch* batch);
  * workgroups start in index order is how the hardware behaves, not a promise: the priority is a hint and changes no result.
  * Per-instance device state that the kernels address by position cannot travel with a permuted batch: a non-NULL
  * pmpc_sqp_settings::filter_state or iteration_trace is refused with PMPC_ERR_INVALID_ARGUMENT before any device call (as
- * pmpc_sqp_solve_batch_multi refuses them). Built-in OCPs only: user-registered OCPs (pmpc_sqp_solve_batch_user) and generic NLPs
- * (pmpc_nlp_*) have no prioritised form. These are new entry points; by the rule above they do not change PMPC_ABI_VERSION. */
+ * pmpc_sqp_solve_batch_multi refuses them). The one-off prioritised solves are for built-in OCPs only: of a user-registered OCP the MPC step
+ * takes a priority (pmpc_mpc_step_batch_user_dev, and pmpc_mpc_batch_set_dispatch on its batch), its one-off solve
+ * (pmpc_sqp_solve_batch_user) and generic NLPs (pmpc_nlp_*) have no prioritised form. These are new entry points; by the rule above they do
+ * not change PMPC_ABI_VERSION. */
 
 /* order[p] = the instance dispatched at position p (B ints, device): by descending priority, each priority clamped to [0, 65535] first
  * (negative values count as 0), equal priorities by ascending instance index. priority: B ints on the device, or NULL for the identity.
@@ -474,6 +478,33 @@ pmpc_status pmpc_sqp_solve_batch_user(pmpc_context* ctx, pmpc_sqp_dev_fn fn, con
                                       const double* lam_guess, const double* d, const double* lbx, const double* ubx,
                                       const double* lbg, const double* ubg, const pmpc_sqp_settings* sqp_settings,
                                       const pmpc_qp_settings* qp_settings, double* x, double* lam, pmpc_sqp_info* info);
+
+/* The receding-horizon step of a registered OCP, everything resident on the device: the contract of pmpc_mpc_step_batch_dev — x0 pinned on the
+ * last nx entries of the x block of lbx / ubx, warm start from x / lam, which are overwritten, u(t_start) to u0 (may be NULL) — with `fn` and
+ * `model` in place of the model id, and the OCP's dimensions given as numbers as for pmpc_sqp_solve_batch_user: nn = P * S + 1,
+ * n = (nx + nu) * nn + np, m = (nx + ng) * nn. priority == NULL: index order. Otherwise the contract of pmpc_mpc_step_batch_prioritised_dev:
+ * the batch is gathered into dispatch order, solved and scattered back, and priority receives iter_weight * iter + qp_solver_iter of this step;
+ * a non-NULL filter_state / iteration_trace is then refused. PMPC_ERR_INVALID_ARGUMENT before any device call for a NULL ctx, fn, model, x0,
+ * lbx, ubx, settings, x, lam or info; nx < 1; nu, np, nd, ng or B < 0; P or S < 1; nd > 0 without d; ng > 0 without lbg / ubg; max_iter < 1; a
+ * regularisation or kkt_form outside 0 .. 2. A status returned by fn is passed through. Linearisation, the one-off prioritised solve and the sharded solve have no registered form. */
+pmpc_status pmpc_mpc_step_batch_user_dev(pmpc_context* ctx, pmpc_sqp_dev_fn fn, const void* model, int nx, int nu, int np, int nd, int ng,
+                                         int P, int S, double t0, double tf, int B, const double* x0, const double* d, double* lbx, double* ubx,
+                                         const double* lbg, const double* ubg, const pmpc_sqp_settings* sqp_settings,
+                                         const pmpc_qp_settings* qp_settings, double* x, double* lam, pmpc_sqp_info* info, double* u0,
+                                         int* priority, int iter_weight);
+/* pmpc_mpc_batch_create for a registered OCP. The batch keeps fn, the five dimensions and its own copy of the model_bytes bytes at `model`
+ * (the object may go away after the call); pmpc_mpc_batch_step / _solution / _set_dispatch / _sample / _shift / _update / _destroy serve the
+ * handle as they serve a built-in one. Refusals as above, and B < 1 or model_bytes == 0. */
+pmpc_status pmpc_mpc_batch_create_user(pmpc_context* ctx, pmpc_sqp_dev_fn fn, const void* model, unsigned long model_bytes, int nx, int nu,
+                                       int np, int nd, int ng, int P, int S, double t0, double tf, int B, const double* d, const double* lbx,
+                                       const double* ubx, const double* lbg, const double* ubg, const double* x_guess, const double* lam_guess,
+                                       pmpc_mpc_batch** batch);
+/* New problem data for a batch of either kind (MPC::set_static_parameters and the bound setters are callable at any time,
+ * mpc_wrapper.hpp:103-187): host arrays of the sizes given at creation — d B*ND, lbx / ubx B*n, lbg / ubg B*NG*nn — are uploaded on the
+ * context's stream, which is then synchronised; a NULL argument keeps what the batch holds. The next step pins x0 again, so lbx / ubx need not
+ * carry it. The iterate stays. Nothing calls this implicitly. */
+pmpc_status pmpc_mpc_batch_update(pmpc_mpc_batch* batch, const double* d, const double* lbx, const double* ubx, const double* lbg,
+                                  const double* ubg);
 
 /* ---- generic NLPs ----------------------------------------------------------------------------------------------------
  * Batched SQPBase::solve for NLPs that are not collocation OCPs: the reference's ProblemBase problems (src/solvers/nlproblem.hpp), with

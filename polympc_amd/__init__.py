@@ -11,5 +11,5 @@ from .capi import (  # noqa: F401
     qp_settings_default, qp_settings_sqp_default, sqp_settings_default,
     MODEL_ROBOT, MODEL_CSTR, MODEL_PARKING, MODEL_ROBOT_NG, MODEL_KITE_STANDIN, MODEL_PARKING_NG,
     QP_SOLVED, QP_MAX_ITER_EXCEEDED, SQP_SOLVED, SQP_MAX_ITER_EXCEEDED, EXPORTED_SYMBOLS,
-    NLP_CONSTRAINED_ROSENBROCK, NLP_ROSENBROCK, NLP_SIMPLE, NLP_HS071, StatusError, UserNLP, nlp_dims,
+    NLP_CONSTRAINED_ROSENBROCK, NLP_ROSENBROCK, NLP_SIMPLE, NLP_HS071, StatusError, UserNLP, nlp_dims, UserOCP, MPCBatch,
 )

@@ -29,6 +29,7 @@ EXPORTED_SYMBOLS = [
     "pmpc_qp_settings_default", "pmpc_qp_settings_sqp_default", "pmpc_sqp_settings_default", "pmpc_chebyshev",
     "pmpc_qp_boxadmm_solve_batch", "pmpc_qp_boxadmm_solve_batch_dev", "pmpc_qp_boxadmm_solve_batch_f32", "pmpc_qp_boxadmm_solve_batch_f32_dev", "pmpc_qp_admm_solve_batch_f32", "pmpc_qp_admm_solve_batch_f32_dev", "pmpc_ocp_dims", "pmpc_ocp_linearise_batch",
     "pmpc_sqp_solve_batch", "pmpc_sqp_solve_batch_dev", "pmpc_sqp_solve_batch_user", "pmpc_sqp_solve_batch_multi",
+    "pmpc_mpc_step_batch_user_dev", "pmpc_mpc_batch_create_user", "pmpc_mpc_batch_update",
     "pmpc_mpc_step_batch_dev", "pmpc_mpc_batch_create", "pmpc_mpc_batch_step", "pmpc_mpc_batch_solution", "pmpc_mpc_batch_destroy",
     "pmpc_dispatch_order_dev", "pmpc_sqp_work_priority_dev", "pmpc_sqp_solve_batch_prioritised", "pmpc_sqp_solve_batch_prioritised_dev",
     "pmpc_mpc_step_batch_prioritised_dev", "pmpc_mpc_batch_set_dispatch",
@@ -108,7 +109,9 @@ def build_library(force=False, verbose=False, jobs=None):
         subprocess.check_call(cmd)
     with ThreadPoolExecutor(max_workers=jobs or min(8, os.cpu_count() or 1)) as ex:
         list(ex.map(run, todo))
-    run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB_PATH] + objs)
+    # the soname lets the loader recognise the library, once loaded from any path, as the `libpolympc_amd.so` that a user's OCP / NLP library was
+    # linked against: UserOCP loads such a library after lib() without an rpath or LD_LIBRARY_PATH
+    run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-Wl,-soname,libpolympc_amd.so", "-o", LIB_PATH] + objs)
     return LIB_PATH
 
 
@@ -231,6 +234,69 @@ class UserNLP:
         return _nlp_host_call(f, lead, B, dm, x_guess, lam_guess, d, lbx, ubx, lbg, ubg, sqp_settings, qp_settings)
 
 
+_USER_OCP_HEAD = [C.c_void_p, C.c_void_p, C.c_void_p]   # ctx, fn, model
+_USER_OCP_GRID = [C.c_int] * 7 + [C.c_double] * 2       # nx, nu, np, nd, ng, P, S, t0, tf
+
+
+class UserOCP:
+    """An OCP registered with PMPC_REGISTER_OCP(name) in a user's shared library: its dimensions (pmpc_user_dims_<name>), its one-off batched
+    solve (pmpc_sqp_solve_batch_user with the library's pmpc_user_sqp_dev_<name>) and its receding-horizon loop on the device
+    (pmpc_mpc_step_batch_user_dev, pmpc_mpc_batch_create_user). `model` is the bytes of the user's model object (copied by value into the
+    kernel; default: 8 zero bytes, for a struct without data members)."""
+
+    def __init__(self, so_path, name, model=None):
+        lib()   # loaded first: the user's library finds the product library it was linked against by its soname, wherever it lies
+        self.so = C.CDLL(os.path.abspath(so_path))
+        self.fn = getattr(self.so, "pmpc_user_sqp_dev_" + name)
+        v = [C.c_int() for _ in range(5)]
+        getattr(self.so, "pmpc_user_dims_" + name)(*[C.byref(a) for a in v])
+        self.nx, self.nu, self.np, self.nd, self.ng = [a.value for a in v]
+        raw = bytes(model) if model is not None else bytes(8)
+        self.model = C.create_string_buffer(raw, len(raw))
+        self.model_bytes = len(raw)
+
+    def dims(self, P, S):
+        """the transcription's dimensions on the (P, S) grid, keyed as ocp_dims"""
+        nn = P * S + 1
+        me, mi = self.nx * nn, self.ng * nn
+        return dict(nx=self.nx, nu=self.nu, np=self.np, nd=self.nd, ng=self.ng, n=(self.nx + self.nu) * nn + self.np, m_eq=me, m_ineq=mi, m=me + mi,
+                    nn=nn)
+
+    def _head(self, ctx):
+        return ctx._ctx, C.cast(self.fn, C.c_void_p), C.cast(self.model, C.c_void_p)
+
+    def _grid(self, P, S, t0, tf):
+        return self.nx, self.nu, self.np, self.nd, self.ng, int(P), int(S), float(t0), float(tf)
+
+    def solve_batch(self, ctx, P, S, t0, tf, B, d, lbx, ubx, lbg=None, ubg=None, x_guess=None, lam_guess=None, sqp_settings=None, qp_settings=None):
+        """pmpc_sqp_solve_batch_user (host buffers) -> x (B, n), lam (B, m + n), info"""
+        dm = self.dims(P, S); n, m = dm["n"], dm["m"]
+        ss = sqp_settings or sqp_settings_default(); qs = qp_settings or qp_settings_sqp_default()
+        x = np.zeros((B, n)); lam = np.zeros((B, m + n)); info = np.zeros(B, dtype=SQP_INFO_DTYPE)
+        keep = [_h(a) for a in (x_guess, lam_guess, d, lbx, ubx, lbg, ubg)]
+        P_ = C.POINTER(C.c_double)
+        f = lib().pmpc_sqp_solve_batch_user
+        f.argtypes = _USER_OCP_HEAD + _USER_OCP_GRID + [C.c_int] + [P_] * 7 + [C.POINTER(SQPSettings), C.POINTER(QPSettings), P_, P_, C.c_void_p]
+        _check_status(f(*self._head(ctx), *self._grid(P, S, t0, tf), int(B), *[k[1] for k in keep], C.byref(ss), C.byref(qs), x.ctypes.data_as(P_),
+                        lam.ctypes.data_as(P_), C.c_void_p(info.ctypes.data)))
+        return x, lam, info
+
+    def mpc_step_batch_dev(self, ctx, P, S, t0, tf, B, x0, d, lbx, ubx, x, lam, info, sqp_settings, qp_settings, u0=None, lbg=None, ubg=None,
+                           priority=None, iter_weight=0):
+        """pmpc_mpc_step_batch_user_dev on torch CUDA tensors; priority: None (index order) or an int32 tensor, read as this step's priorities and
+        overwritten with iter_weight * iter + qp_solver_iter of this step's solve. Asynchronous on the context's stream."""
+        P_ = C.POINTER(C.c_double)
+        f = lib().pmpc_mpc_step_batch_user_dev
+        f.argtypes = _USER_OCP_HEAD + _USER_OCP_GRID + [C.c_int] + [P_] * 6 + [C.POINTER(SQPSettings), C.POINTER(QPSettings), P_, P_, C.c_void_p, P_,
+                                                                                C.c_void_p, C.c_int]
+        _check_status(f(*self._head(ctx), *self._grid(P, S, t0, tf), int(B), _d(x0), _d(d), _d(lbx), _d(ubx), _d(lbg), _d(ubg), C.byref(sqp_settings),
+                        C.byref(qp_settings), _d(x), _d(lam), C.c_void_p(info.data_ptr()), _d(u0), _dv(priority), int(iter_weight)))
+
+    def mpc_batch(self, ctx, P, S, t0, tf, B, d, lbx, ubx, lbg=None, ubg=None, x_guess=None, lam_guess=None):
+        """pmpc_mpc_batch_create_user: B controllers of this OCP whose data stay on the device between steps (MPCBatch)"""
+        return MPCBatch(ctx, self, P, S, t0, tf, B, d, lbx, ubx, lbg, ubg, x_guess, lam_guess)
+
+
 def _h(a):
     """host array -> (keepalive, pointer)"""
     if a is None:
@@ -259,14 +325,34 @@ class MPCBatch:
     """pmpc_mpc_batch: host arrays in and out, everything else resident (pmpc_mpc_batch_create / _step / _solution / _set_dispatch / _destroy)."""
 
     def __init__(self, ctx, model, P, S, t0, tf, B, d, lbx, ubx, lbg=None, ubg=None, x_guess=None, lam_guess=None, mparams=None):
-        self.dims = ocp_dims(model, P, S); self.B = int(B)
+        """model: a built-in model id, or a UserOCP (pmpc_mpc_batch_create_user; mparams is then not used: the parameters are the UserOCP's
+        model object)"""
+        self.B = int(B)
         self._batch = C.c_void_p()
-        keep = [_h(a) for a in (mparams, d, lbx, ubx, lbg, ubg, x_guess, lam_guess)]
         P_ = C.POINTER(C.c_double)
+        if isinstance(model, UserOCP):
+            self.dims = model.dims(P, S)
+            keep = [_h(a) for a in (d, lbx, ubx, lbg, ubg, x_guess, lam_guess)]
+            f = lib().pmpc_mpc_batch_create_user
+            f.argtypes = _USER_OCP_HEAD + [C.c_ulong] + _USER_OCP_GRID + [C.c_int] + [P_] * 7 + [C.POINTER(C.c_void_p)]
+            _check_status(f(*model._head(ctx), model.model_bytes, *model._grid(P, S, t0, tf), self.B, *[k[1] for k in keep], C.byref(self._batch)))
+            return
+        self.dims = ocp_dims(model, P, S)
+        keep = [_h(a) for a in (mparams, d, lbx, ubx, lbg, ubg, x_guess, lam_guess)]
         f = lib().pmpc_mpc_batch_create
         f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, P_, C.c_int, C.c_int] + [P_] * 7 + [C.POINTER(C.c_void_p)]
         _check_status(f(ctx._ctx, model, P, S, t0, tf, keep[0][1], 0 if keep[0][0] is None else len(keep[0][0]), self.B, *[k[1] for k in keep[1:]],
                         C.byref(self._batch)))
+
+    def update(self, d=None, lbx=None, ubx=None, lbg=None, ubg=None):
+        """pmpc_mpc_batch_update: new static parameters / bounds (host arrays of the sizes given at creation; None keeps what the batch holds)"""
+        keep = [_h(a) for a in (d, lbx, ubx, lbg, ubg)]
+        dm = self.dims
+        for (a, _), per in zip(keep, (dm["nd"], dm["n"], dm["n"], dm["m_ineq"], dm["m_ineq"])):
+            assert a is None or a.size == self.B * per, "an array of another size than at creation"
+        f = lib().pmpc_mpc_batch_update
+        f.argtypes = [C.c_void_p] + [C.POINTER(C.c_double)] * 5
+        _check_status(f(self._batch, *[k[1] for k in keep]))
 
     def set_dispatch(self, mode, iter_weight=0):
         """pmpc_mpc_batch_set_dispatch: 0 index order (default), 1 longest first by the previous step's counts"""

@@ -315,19 +315,53 @@ __global__ void mpc_first_control_kernel(int B, int n, int varx, int nu, int nn,
     const int b = idx / nu, i = idx - b * nu;
     u0[idx] = x[(size_t)b * n + varx + (size_t)(nn - 1) * nu + i];
 }
-pmpc_status pmpc_mpc_step_batch_dev(pmpc_context* ctx, int model, int P, int S, double t0, double tf, const double* mparams, int n_mparams,
-                                    int B, const double* x0, const double* d, double* lbx, double* ubx, const double* lbg,
-                                    const double* ubg, const pmpc_sqp_settings* ss, const pmpc_qp_settings* qs, double* x, double* lam,
-                                    pmpc_sqp_info* info, double* u0) {
-    if (!ctx || B < 0 || !x0 || !lbx || !ubx || !ss || !qs || !x || !lam || !info) return PMPC_ERR_INVALID_ARGUMENT;
-    if (B == 0) return PMPC_OK;
-    int nx, nu, np, nd, ng, n, me, mi;
-    pmpc_status st = pmpc_ocp_dims(model, P, S, &nx, &nu, &np, &nd, &ng, &n, &me, &mi);
-    if (st != PMPC_OK) return st;
-    if ((nd > 0 && !d) || ss->max_iter < 1) return PMPC_ERR_INVALID_ARGUMENT;
+/* How a batch is solved on device buffers, and on which grid: a built-in model id with its parameters, or (fn != NULL) the device entry and the
+ * model object of a registered OCP. The MPC step, the dispatch-order solve and the opaque batch are written against this, not against a model id. */
+struct DevSolver {
+    int model; const double* mparams; int n_mparams; pmpc_sqp_dev_fn fn; const void* user; int P, S; double t0, tf;
+    pmpc_status operator()(pmpc_context* ctx, int B, const double* x_guess, const double* lam_guess, const double* d, const double* lbx, const double* ubx,
+                           const double* lbg, const double* ubg, const pmpc_sqp_settings* ss, const pmpc_qp_settings* qs, double* x, double* lam,
+                           pmpc_sqp_info* info) const {
+        if (fn) return fn(ctx, user, P, S, t0, tf, B, x_guess, lam_guess, d, lbx, ubx, lbg, ubg, ss, qs, x, lam, info);
+        return pmpc_sqp_solve_batch_dev(ctx, model, P, S, t0, tf, mparams, n_mparams, B, x_guess, lam_guess, d, lbx, ubx, lbg, ubg, ss, qs, x, lam, info);
+    }
+};
+static DevSolver builtin_solver(int model, int P, int S, double t0, double tf, const double* mparams, int n_mparams) {
+    return DevSolver{model, mparams, n_mparams, nullptr, nullptr, P, S, t0, tf};
+}
+// the transcription's sizes: of a built-in model from pmpc_ocp_dims, of a registered OCP from the caller's numbers
+struct OcpSizes { int nx, nu, np, nd, ng, nn, n, m, mi; };
+static pmpc_status builtin_sizes(int model, int P, int S, OcpSizes* z) {
+    int me;
+    const pmpc_status st = pmpc_ocp_dims(model, P, S, &z->nx, &z->nu, &z->np, &z->nd, &z->ng, &z->n, &me, &z->mi);
+    z->nn = P * S + 1; z->m = me + z->mi;
+    return st;
+}
+static OcpSizes user_sizes(int nx, int nu, int np, int nd, int ng, int P, int S) {
+    const int nn = P * S + 1;
+    return OcpSizes{nx, nu, np, nd, ng, nn, (nx + nu) * nn + np, (nx + ng) * nn, ng * nn};
+}
+
+// what the MPC step adds to the scatter: u(t_start) from the staged x, and the work of this solve as the next step's priority
+struct MpcScatter { double* u0; int nu, u_off; int* priority; int iter_weight; };
+static pmpc_status solve_in_dispatch_order(pmpc_context* ctx, const DevSolver& solve, int B, int n, int m, int nd, int mi, const double* x_guess,
+                                           const double* lam_guess, const double* d, const double* lbx, const double* ubx, const double* lbg,
+                                           const double* ubg, const pmpc_sqp_settings* ss, const pmpc_qp_settings* qs, double* x, double* lam,
+                                           pmpc_sqp_info* info, const int* priority, const MpcScatter* mpc);
+
+/* The one body of the receding-horizon step, behind every MPC entry point. Validated arguments, B >= 1. priority == NULL: index order. */
+static pmpc_status mpc_step(pmpc_context* ctx, const DevSolver& solve, const OcpSizes& z, int B, const double* x0, const double* d, double* lbx,
+                            double* ubx, const double* lbg, const double* ubg, const pmpc_sqp_settings* ss, const pmpc_qp_settings* qs, double* x,
+                            double* lam, pmpc_sqp_info* info, double* u0, int* priority, int iter_weight) {
     HIPCHK(hipSetDevice(ctx->device));
-    const int m = me + mi, nn = P * S + 1, varx = nx * nn;
-    hipLaunchKernelGGL(mpc_pin_initial_state_kernel, dim3((B * nx + 255) / 256), dim3(256), 0, ctx->stream, B, n, varx, nx, x0, lbx, ubx);
+    const int n = z.n, m = z.m, varx = z.nx * z.nn;
+    hipLaunchKernelGGL(mpc_pin_initial_state_kernel, dim3((B * z.nx + 255) / 256), dim3(256), 0, ctx->stream, B, n, varx, z.nx, x0, lbx, ubx);
+    if (priority) {
+        HIPCHK(hipGetLastError());
+        // warm start from the current x / lam: the gather into dispatch order is the copy that keeps guess and result apart
+        const MpcScatter mpc{u0, z.nu, varx + (z.nn - 1) * z.nu, priority, iter_weight};
+        return solve_in_dispatch_order(ctx, solve, B, n, m, z.nd, z.mi, x, lam, d, lbx, ubx, lbg, ubg, ss, qs, x, lam, info, priority, &mpc);
+    }
     // warm start: the previous solution is the guess (SQPBase::solve() starts from m_x / m_lam, sqp_base.hpp:569-581); the
     // kernel's guess and result pointers must not alias, so the guess is a device-to-device copy
     Staging stg(ctx);
@@ -335,16 +369,30 @@ pmpc_status pmpc_mpc_step_batch_dev(pmpc_context* ctx, int model, int P, int S, 
     if (!stg.ok()) return stg.status;
     HIPCHK(hipMemcpyAsync(xg, x, (size_t)B * n * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
     HIPCHK(hipMemcpyAsync(lg, lam, (size_t)B * (m + n) * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-    st = pmpc_sqp_solve_batch_dev(ctx, model, P, S, t0, tf, mparams, n_mparams, B, xg, lg, d, lbx, ubx, lbg, ubg, ss, qs, x, lam, info);
+    const pmpc_status st = solve(ctx, B, xg, lg, d, lbx, ubx, lbg, ubg, ss, qs, x, lam, info);
     if (st != PMPC_OK) return st;
-    if (u0) hipLaunchKernelGGL(mpc_first_control_kernel, dim3((B * nu + 255) / 256), dim3(256), 0, ctx->stream, B, n, varx, nu, nn, x, u0);
+    if (u0) hipLaunchKernelGGL(mpc_first_control_kernel, dim3((B * z.nu + 255) / 256), dim3(256), 0, ctx->stream, B, n, varx, z.nu, z.nn, x, u0);
     HIPCHK(hipGetLastError());
     return PMPC_OK;
 }
 
+pmpc_status pmpc_mpc_step_batch_dev(pmpc_context* ctx, int model, int P, int S, double t0, double tf, const double* mparams, int n_mparams,
+                                    int B, const double* x0, const double* d, double* lbx, double* ubx, const double* lbg,
+                                    const double* ubg, const pmpc_sqp_settings* ss, const pmpc_qp_settings* qs, double* x, double* lam,
+                                    pmpc_sqp_info* info, double* u0) {
+    if (!ctx || B < 0 || !x0 || !lbx || !ubx || !ss || !qs || !x || !lam || !info) return PMPC_ERR_INVALID_ARGUMENT;
+    if (B == 0) return PMPC_OK;
+    OcpSizes z;
+    const pmpc_status st = builtin_sizes(model, P, S, &z);
+    if (st != PMPC_OK) return st;
+    if ((z.nd > 0 && !d) || ss->max_iter < 1) return PMPC_ERR_INVALID_ARGUMENT;
+    return mpc_step(ctx, builtin_solver(model, P, S, t0, tf, mparams, n_mparams), z, B, x0, d, lbx, ubx, lbg, ubg, ss, qs, x, lam, info, u0, nullptr, 0);
+}
+
 /* ---- a batch of MPC controllers whose state lives on the device between steps (host-side callers without HIP) ---- */
 struct pmpc_mpc_batch {
-    pmpc_context* ctx; int model, P, S, B, nx, nu, nd, n, m, mi; double t0, tf; std::vector<double> mparams;
+    pmpc_context* ctx; DevSolver solve; OcpSizes z; int B;
+    std::vector<double> mparams; std::vector<unsigned char> user;   // what solve.mparams / solve.user point to: the batch's own copies
     double *d = nullptr, *lbx = nullptr, *ubx = nullptr, *lbg = nullptr, *ubg = nullptr, *x = nullptr, *lam = nullptr, *x0 = nullptr, *u0 = nullptr;
     pmpc_sqp_info* info = nullptr;
     int dispatch_mode = 0, iter_weight = 0; int* priority = nullptr; bool stepped = false;   // pmpc_mpc_batch_set_dispatch
@@ -358,17 +406,16 @@ pmpc_status pmpc_mpc_batch_destroy(pmpc_mpc_batch* h) {
     delete h;
     return PMPC_OK;
 }
-pmpc_status pmpc_mpc_batch_create(pmpc_context* ctx, int model, int P, int S, double t0, double tf, const double* mparams, int n_mparams, int B,
-                                  const double* d, const double* lbx, const double* ubx, const double* lbg, const double* ubg,
-                                  const double* x_guess, const double* lam_guess, pmpc_mpc_batch** out) {
-    if (!ctx || !out || B < 1 || !lbx || !ubx) return PMPC_ERR_INVALID_ARGUMENT;
-    int nx, nu, np, nd, ng, n, me, mi;
-    pmpc_status st = pmpc_ocp_dims(model, P, S, &nx, &nu, &np, &nd, &ng, &n, &me, &mi);
-    if (st != PMPC_OK) return st;
-    if ((nd > 0 && !d) || (mi > 0 && (!lbg || !ubg))) return PMPC_ERR_INVALID_ARGUMENT;
+// Validated arguments. The batch takes its own copies of the model parameters resp. the user's model object (user_bytes of them).
+static pmpc_status mpc_batch_create(pmpc_context* ctx, const DevSolver& solve, size_t user_bytes, const OcpSizes& z, int B, const double* d,
+                                    const double* lbx, const double* ubx, const double* lbg, const double* ubg, const double* x_guess,
+                                    const double* lam_guess, pmpc_mpc_batch** out) {
     HIPCHK(hipSetDevice(ctx->device));
-    pmpc_mpc_batch* h = new pmpc_mpc_batch{ctx, model, P, S, B, nx, nu, nd, n, me + mi, mi, t0, tf, std::vector<double>(mparams ? mparams : nullptr, mparams ? mparams + n_mparams : nullptr)};
-    const size_t Bn = (size_t)B * n, Bd = (size_t)B * (n + h->m);
+    pmpc_mpc_batch* h = new pmpc_mpc_batch{ctx, solve, z, B};
+    if (solve.fn) { h->user.assign((const unsigned char*)solve.user, (const unsigned char*)solve.user + user_bytes); h->solve.user = h->user.data(); }
+    else { if (solve.mparams) h->mparams.assign(solve.mparams, solve.mparams + solve.n_mparams); h->solve.mparams = h->mparams.empty() ? nullptr : h->mparams.data(); h->solve.n_mparams = (int)h->mparams.size(); }
+    const int nx = z.nx, nu = z.nu, nd = z.nd, n = z.n, mi = z.mi;
+    const size_t Bn = (size_t)B * n, Bd = (size_t)B * (n + z.m);
     auto up = [&](double** dst, const double* src, size_t count, bool zero) -> bool {
         if (hipMalloc((void**)dst, (count ? count : 1) * sizeof(double)) != hipSuccess) return false;
         if (src) return hipMemcpyAsync(*dst, src, count * sizeof(double), hipMemcpyHostToDevice, ctx->stream) == hipSuccess;
@@ -383,21 +430,58 @@ pmpc_status pmpc_mpc_batch_create(pmpc_context* ctx, int model, int P, int S, do
     *out = h;
     return PMPC_OK;
 }
+pmpc_status pmpc_mpc_batch_create(pmpc_context* ctx, int model, int P, int S, double t0, double tf, const double* mparams, int n_mparams, int B,
+                                  const double* d, const double* lbx, const double* ubx, const double* lbg, const double* ubg,
+                                  const double* x_guess, const double* lam_guess, pmpc_mpc_batch** out) {
+    if (!ctx || !out || B < 1 || !lbx || !ubx) return PMPC_ERR_INVALID_ARGUMENT;
+    OcpSizes z;
+    const pmpc_status st = builtin_sizes(model, P, S, &z);
+    if (st != PMPC_OK) return st;
+    if ((z.nd > 0 && !d) || (z.mi > 0 && (!lbg || !ubg))) return PMPC_ERR_INVALID_ARGUMENT;
+    return mpc_batch_create(ctx, builtin_solver(model, P, S, t0, tf, mparams, n_mparams), 0, z, B, d, lbx, ubx, lbg, ubg, x_guess, lam_guess, out);
+}
+
+/* The argument check of the registered OCP's MPC entry points, run before the first device call. The grid limits are the launcher's own
+ * (sqp_launch_dev answers them the same way), asked here because the sizes of the copies and of the staging derive from them. */
+static pmpc_status check_user_mpc_args(pmpc_context* ctx, pmpc_sqp_dev_fn fn, const void* model, int nx, int nu, int np, int nd, int ng, int P, int S,
+                                       int B, const double* d, const double* lbx, const double* ubx, const double* lbg, const double* ubg) {
+    if (!ctx || !fn || !model || !lbx || !ubx || nx < 1 || nu < 0 || np < 0 || nd < 0 || ng < 0 || P < 1 || S < 1 || B < 0) return PMPC_ERR_INVALID_ARGUMENT;
+    if ((nd > 0 && !d) || (ng > 0 && (!lbg || !ubg))) return PMPC_ERR_INVALID_ARGUMENT;
+    if (P > MAX_P || S > MAX_NODES || P * S + 1 > MAX_NODES) return PMPC_ERR_UNSUPPORTED_SIZE;
+    return PMPC_OK;
+}
+pmpc_status pmpc_mpc_batch_create_user(pmpc_context* ctx, pmpc_sqp_dev_fn fn, const void* model, unsigned long model_bytes, int nx, int nu, int np,
+                                       int nd, int ng, int P, int S, double t0, double tf, int B, const double* d, const double* lbx,
+                                       const double* ubx, const double* lbg, const double* ubg, const double* x_guess, const double* lam_guess,
+                                       pmpc_mpc_batch** out) {
+    if (!out || B < 1 || model_bytes == 0) return PMPC_ERR_INVALID_ARGUMENT;
+    const pmpc_status chk = check_user_mpc_args(ctx, fn, model, nx, nu, np, nd, ng, P, S, B, d, lbx, ubx, lbg, ubg);
+    if (chk != PMPC_OK) return chk;
+    return mpc_batch_create(ctx, DevSolver{0, nullptr, 0, fn, model, P, S, t0, tf}, (size_t)model_bytes, user_sizes(nx, nu, np, nd, ng, P, S), B, d, lbx,
+                            ubx, lbg, ubg, x_guess, lam_guess, out);
+}
 pmpc_status pmpc_mpc_batch_step(pmpc_mpc_batch* h, const double* x0, const pmpc_sqp_settings* ss, const pmpc_qp_settings* qs, double* u0,
                                 pmpc_sqp_info* info) {
     if (!h || !x0 || !ss || !qs) return PMPC_ERR_INVALID_ARGUMENT;
     pmpc_context* ctx = h->ctx;
+    const DevSolver& sv = h->solve;
+    const OcpSizes& z = h->z;
     HIPCHK(hipSetDevice(ctx->device));
-    HIPCHK(hipMemcpyAsync(h->x0, x0, (size_t)h->B * h->nx * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    const double* mp = h->mparams.empty() ? nullptr : h->mparams.data();
-    pmpc_status st = h->dispatch_mode == 1
-        ? pmpc_mpc_step_batch_prioritised_dev(ctx, h->model, h->P, h->S, h->t0, h->tf, mp, (int)h->mparams.size(), h->B, h->x0, h->d, h->lbx, h->ubx, h->lbg,
-                                              h->ubg, ss, qs, h->x, h->lam, h->info, h->u0, h->priority, h->iter_weight)
-        : pmpc_mpc_step_batch_dev(ctx, h->model, h->P, h->S, h->t0, h->tf, mp, (int)h->mparams.size(), h->B, h->x0, h->d, h->lbx, h->ubx, h->lbg, h->ubg,
-                                  ss, qs, h->x, h->lam, h->info, h->u0);
+    HIPCHK(hipMemcpyAsync(h->x0, x0, (size_t)h->B * z.nx * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    // through the public entry points: their argument checks are the step's
+    pmpc_status st;
+    if (sv.fn)
+        st = pmpc_mpc_step_batch_user_dev(ctx, sv.fn, sv.user, z.nx, z.nu, z.np, z.nd, z.ng, sv.P, sv.S, sv.t0, sv.tf, h->B, h->x0, h->d, h->lbx, h->ubx, h->lbg,
+                                          h->ubg, ss, qs, h->x, h->lam, h->info, h->u0, h->dispatch_mode == 1 ? h->priority : nullptr, h->iter_weight);
+    else if (h->dispatch_mode == 1)
+        st = pmpc_mpc_step_batch_prioritised_dev(ctx, sv.model, sv.P, sv.S, sv.t0, sv.tf, sv.mparams, sv.n_mparams, h->B, h->x0, h->d, h->lbx, h->ubx, h->lbg,
+                                                 h->ubg, ss, qs, h->x, h->lam, h->info, h->u0, h->priority, h->iter_weight);
+    else
+        st = pmpc_mpc_step_batch_dev(ctx, sv.model, sv.P, sv.S, sv.t0, sv.tf, sv.mparams, sv.n_mparams, h->B, h->x0, h->d, h->lbx, h->ubx, h->lbg, h->ubg,
+                                     ss, qs, h->x, h->lam, h->info, h->u0);
     if (st != PMPC_OK) return st;
     h->stepped = true;
-    if (u0) HIPCHK(hipMemcpyAsync(u0, h->u0, (size_t)h->B * h->nu * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (u0) HIPCHK(hipMemcpyAsync(u0, h->u0, (size_t)h->B * z.nu * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     if (info) HIPCHK(hipMemcpyAsync(info, h->info, (size_t)h->B * sizeof(pmpc_sqp_info), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return PMPC_OK;
@@ -405,9 +489,21 @@ pmpc_status pmpc_mpc_batch_step(pmpc_mpc_batch* h, const double* x0, const pmpc_
 pmpc_status pmpc_mpc_batch_solution(pmpc_mpc_batch* h, double* x, double* lam) {
     if (!h) return PMPC_ERR_INVALID_ARGUMENT;
     HIPCHK(hipSetDevice(h->ctx->device));
-    if (x) HIPCHK(hipMemcpyAsync(x, h->x, (size_t)h->B * h->n * sizeof(double), hipMemcpyDeviceToHost, h->ctx->stream));
-    if (lam) HIPCHK(hipMemcpyAsync(lam, h->lam, (size_t)h->B * (h->n + h->m) * sizeof(double), hipMemcpyDeviceToHost, h->ctx->stream));
+    if (x) HIPCHK(hipMemcpyAsync(x, h->x, (size_t)h->B * h->z.n * sizeof(double), hipMemcpyDeviceToHost, h->ctx->stream));
+    if (lam) HIPCHK(hipMemcpyAsync(lam, h->lam, (size_t)h->B * (h->z.n + h->z.m) * sizeof(double), hipMemcpyDeviceToHost, h->ctx->stream));
     HIPCHK(hipStreamSynchronize(h->ctx->stream));
+    return PMPC_OK;
+}
+pmpc_status pmpc_mpc_batch_update(pmpc_mpc_batch* h, const double* d, const double* lbx, const double* ubx, const double* lbg, const double* ubg) {
+    if (!h) return PMPC_ERR_INVALID_ARGUMENT;
+    pmpc_context* ctx = h->ctx;
+    HIPCHK(hipSetDevice(ctx->device));
+    const size_t Bz = (size_t)h->B;
+    const struct { double* dst; const double* src; size_t count; } ups[] = {
+        {h->d, d, Bz * h->z.nd}, {h->lbx, lbx, Bz * h->z.n}, {h->ubx, ubx, Bz * h->z.n}, {h->lbg, lbg, Bz * h->z.mi}, {h->ubg, ubg, Bz * h->z.mi}};
+    for (const auto& u : ups)
+        if (u.src && u.dst && u.count) HIPCHK(hipMemcpyAsync(u.dst, u.src, u.count * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
     return PMPC_OK;
 }
 
@@ -446,15 +542,11 @@ pmpc_status pmpc_sqp_work_priority_dev(pmpc_context* ctx, int B, const pmpc_sqp_
 // per-instance device state that the kernels address by position cannot travel with a permuted batch
 static bool has_positional_state(const pmpc_sqp_settings* ss) { return ss->filter_state || ss->iteration_trace; }
 
-// what the MPC step adds to the scatter: u(t_start) from the staged x, and the work of this solve as the next step's priority
-struct MpcScatter { double* u0; int nu, u_off; int* priority; int iter_weight; };
-
 // Validated arguments, B >= 1, priority non-null. The input blocks that exist (non-null, non-empty) are gathered; the others reach the launcher as given.
-static pmpc_status solve_in_dispatch_order(pmpc_context* ctx, int model, int P, int S, double t0, double tf, const double* mparams, int n_mparams, int B,
-                                           int n, int m, int nd, int mi, const double* x_guess, const double* lam_guess, const double* d,
-                                           const double* lbx, const double* ubx, const double* lbg, const double* ubg, const pmpc_sqp_settings* ss,
-                                           const pmpc_qp_settings* qs, double* x, double* lam, pmpc_sqp_info* info, const int* priority,
-                                           const MpcScatter* mpc) {
+static pmpc_status solve_in_dispatch_order(pmpc_context* ctx, const DevSolver& solve, int B, int n, int m, int nd, int mi, const double* x_guess,
+                                           const double* lam_guess, const double* d, const double* lbx, const double* ubx, const double* lbg,
+                                           const double* ubg, const pmpc_sqp_settings* ss, const pmpc_qp_settings* qs, double* x, double* lam,
+                                           pmpc_sqp_info* info, const int* priority, const MpcScatter* mpc) {
     HIPCHK(hipSetDevice(ctx->device));
     Staging stg(ctx);
     const size_t Bz = (size_t)B;
@@ -472,8 +564,7 @@ static pmpc_status solve_in_dispatch_order(pmpc_context* ctx, int model, int P, 
     in.add(x_guess, sxg, n); in.add(lam_guess, slg, m + n); in.add(d, sd, nd); in.add(lbx, slbx, n); in.add(ubx, subx, n); in.add(lbg, slbg, mi); in.add(ubg, subg, mi);
     st = pmpc_internal_dispatch_gather(ctx, B, order, &in);
     if (st != PMPC_OK) return st;
-    st = pmpc_sqp_solve_batch_dev(ctx, model, P, S, t0, tf, mparams, n_mparams, B, sxg, slg, sd ? sd : d, slbx, subx, slbg ? slbg : lbg, subg ? subg : ubg,
-                                  ss, qs, sx, slam, sinfo);
+    st = solve(ctx, B, sxg, slg, sd ? sd : d, slbx, subx, slbg ? slbg : lbg, subg ? subg : ubg, ss, qs, sx, slam, sinfo);
     if (st != PMPC_OK) return st;
     DispatchBlocks out;
     out.add(sx, x, n); out.add(slam, lam, m + n); out.add(sinfo, info, (int)(sizeof(pmpc_sqp_info) / sizeof(unsigned long long)));
@@ -492,8 +583,8 @@ pmpc_status pmpc_sqp_solve_batch_prioritised_dev(pmpc_context* ctx, int model, i
     if (has_positional_state(ss)) return PMPC_ERR_INVALID_ARGUMENT;
     if (B == 0) return PMPC_OK;
     if (!priority) return pmpc_sqp_solve_batch_dev(ctx, model, P, S, t0, tf, mparams, n_mparams, B, x_guess, lam_guess, d, lbx, ubx, lbg, ubg, ss, qs, x, lam, info);
-    return solve_in_dispatch_order(ctx, model, P, S, t0, tf, mparams, n_mparams, B, n, me + mi, nd, mi, x_guess, lam_guess, d, lbx, ubx, lbg, ubg, ss, qs,
-                                   x, lam, info, priority, nullptr);
+    return solve_in_dispatch_order(ctx, builtin_solver(model, P, S, t0, tf, mparams, n_mparams), B, n, me + mi, nd, mi, x_guess, lam_guess, d, lbx, ubx, lbg,
+                                   ubg, ss, qs, x, lam, info, priority, nullptr);
 }
 
 pmpc_status pmpc_sqp_solve_batch_prioritised(pmpc_context* ctx, int model, int P, int S, double t0, double tf, const double* mparams,
@@ -525,17 +616,24 @@ pmpc_status pmpc_mpc_step_batch_prioritised_dev(pmpc_context* ctx, int model, in
     if (has_positional_state(ss)) return PMPC_ERR_INVALID_ARGUMENT;
     if (B == 0) return PMPC_OK;
     if (!priority) return pmpc_mpc_step_batch_dev(ctx, model, P, S, t0, tf, mparams, n_mparams, B, x0, d, lbx, ubx, lbg, ubg, ss, qs, x, lam, info, u0);
-    int nx, nu, np, nd, ng, n, me, mi;
-    const pmpc_status ds = pmpc_ocp_dims(model, P, S, &nx, &nu, &np, &nd, &ng, &n, &me, &mi);
+    OcpSizes z;
+    const pmpc_status ds = builtin_sizes(model, P, S, &z);
     if (ds != PMPC_OK) return ds;
-    HIPCHK(hipSetDevice(ctx->device));
-    const int nn = P * S + 1, varx = nx * nn;
-    hipLaunchKernelGGL(mpc_pin_initial_state_kernel, dim3((B * nx + 255) / 256), dim3(256), 0, ctx->stream, B, n, varx, nx, x0, lbx, ubx);
-    HIPCHK(hipGetLastError());
-    // warm start from the current x / lam: the gather into dispatch order is the copy that keeps guess and result apart
-    const MpcScatter mpc{u0, nu, varx + (nn - 1) * nu, priority, iter_weight};
-    return solve_in_dispatch_order(ctx, model, P, S, t0, tf, mparams, n_mparams, B, n, me + mi, nd, mi, x, lam, d, lbx, ubx, lbg, ubg, ss, qs, x, lam, info,
-                                   priority, &mpc);
+    return mpc_step(ctx, builtin_solver(model, P, S, t0, tf, mparams, n_mparams), z, B, x0, d, lbx, ubx, lbg, ubg, ss, qs, x, lam, info, u0, priority, iter_weight);
+}
+
+pmpc_status pmpc_mpc_step_batch_user_dev(pmpc_context* ctx, pmpc_sqp_dev_fn fn, const void* model, int nx, int nu, int np, int nd, int ng, int P, int S,
+                                         double t0, double tf, int B, const double* x0, const double* d, double* lbx, double* ubx, const double* lbg,
+                                         const double* ubg, const pmpc_sqp_settings* ss, const pmpc_qp_settings* qs, double* x, double* lam,
+                                         pmpc_sqp_info* info, double* u0, int* priority, int iter_weight) {
+    if (!x0 || !ss || !qs || !x || !lam || !info) return PMPC_ERR_INVALID_ARGUMENT;
+    if (ss->max_iter < 1 || (priority && has_positional_state(ss))) return PMPC_ERR_INVALID_ARGUMENT;
+    if (ss->regularisation < 0 || ss->regularisation > 2 || ss->kkt_form < 0 || ss->kkt_form > 2 || (ss->iteration_trace && ss->iteration_trace_capacity < 1))
+        return PMPC_ERR_INVALID_ARGUMENT;   // (what check_sqp_args refuses for a built-in model)
+    const pmpc_status chk = check_user_mpc_args(ctx, fn, model, nx, nu, np, nd, ng, P, S, B, d, lbx, ubx, lbg, ubg);
+    if (chk != PMPC_OK || B == 0) return chk;
+    return mpc_step(ctx, DevSolver{0, nullptr, 0, fn, model, P, S, t0, tf}, user_sizes(nx, nu, np, nd, ng, P, S), B, x0, d, lbx, ubx, lbg, ubg, ss, qs, x, lam,
+                    info, u0, priority, iter_weight);
 }
 
 pmpc_status pmpc_mpc_batch_set_dispatch(pmpc_mpc_batch* h, int mode, int iter_weight) {
@@ -556,28 +654,24 @@ pmpc_status pmpc_mpc_batch_set_dispatch(pmpc_mpc_batch* h, int mode, int iter_we
 pmpc_status pmpc_mpc_batch_sample(pmpc_mpc_batch* h, int K, const double* t, int t_per_instance, double* xs, double* us) {
     if (!h || K < 1 || !t || (!xs && !us) || (t_per_instance != 0 && t_per_instance != 1)) return PMPC_ERR_INVALID_ARGUMENT;
     pmpc_context* ctx = h->ctx;
-    int np = 0;
-    pmpc_status st = pmpc_ocp_dims(h->model, h->P, h->S, nullptr, nullptr, &np, nullptr, nullptr, nullptr, nullptr, nullptr);
-    if (st != PMPC_OK) return st;
+    const OcpSizes& z = h->z;   // (the batch's own dimensions: a registered OCP has no model id to ask)
     HIPCHK(hipSetDevice(ctx->device));
     Staging stg(ctx);   // (the QP range of the staging slots: nothing else of this context is live during the call)
     const size_t Bz = (size_t)h->B;
     const double* dt = stg.in(SLOT_QP_H, t, t_per_instance ? Bz * K : (size_t)K);
-    double* dxs = xs ? stg.out<double>(SLOT_QP_G, Bz * K * h->nx) : nullptr;
-    double* dus = us ? stg.out<double>(SLOT_QP_A, Bz * K * h->nu) : nullptr;
+    double* dxs = xs ? stg.out<double>(SLOT_QP_G, Bz * K * z.nx) : nullptr;
+    double* dus = us ? stg.out<double>(SLOT_QP_A, Bz * K * z.nu) : nullptr;
     if (!stg.ok()) return stg.status;
-    st = pmpc_traj_sample_batch_dev(ctx, h->B, h->nx, h->nu, np, h->P, h->S, h->t0, h->tf, h->x, K, dt, t_per_instance, dxs, dus);
+    const pmpc_status st = pmpc_traj_sample_batch_dev(ctx, h->B, z.nx, z.nu, z.np, h->solve.P, h->solve.S, h->solve.t0, h->solve.tf, h->x, K, dt, t_per_instance, dxs, dus);
     if (st != PMPC_OK) return st;
-    if (xs) stg.fetch(xs, dxs, Bz * K * h->nx);
-    if (us) stg.fetch(us, dus, Bz * K * h->nu);
+    if (xs) stg.fetch(xs, dxs, Bz * K * z.nx);
+    if (us) stg.fetch(us, dus, Bz * K * z.nu);
     return stg.sync();
 }
 pmpc_status pmpc_mpc_batch_shift(pmpc_mpc_batch* h, double dt, int shift_duals) {
     if (!h || !(dt >= 0.0 && dt <= 1.7976931348623157e308)) return PMPC_ERR_INVALID_ARGUMENT;   // (a bad dt is refused before the handle is read)
-    int np = 0, ng = 0;
-    const pmpc_status st = pmpc_ocp_dims(h->model, h->P, h->S, nullptr, nullptr, &np, nullptr, &ng, nullptr, nullptr, nullptr);
-    if (st != PMPC_OK) return st;
-    return pmpc_traj_shift_batch_dev(h->ctx, h->B, h->nx, h->nu, np, ng, h->P, h->S, h->t0, h->tf, dt, h->x, shift_duals ? h->lam : nullptr);
+    const OcpSizes& z = h->z;
+    return pmpc_traj_shift_batch_dev(h->ctx, h->B, z.nx, z.nu, z.np, z.ng, h->solve.P, h->solve.S, h->solve.t0, h->solve.tf, dt, h->x, shift_duals ? h->lam : nullptr);
 }
 
 /* contiguous shards over n_ctx contexts, one PERSISTENT host thread per context (started on the context's first sharded call, joined
