@@ -1,5 +1,8 @@
 // polympc_amd — SQP / linearisation kernels and their launch templates. Included by pmpc_api.hip for the built-in OCPs
 // and by include/polympc/register_ocp.hpp for user-defined OCPs (compiled by hipcc in the user's translation unit).
+// Kernels: sqp_kernel<Model, NN, MM, V>, sqp_kernel_rr<Model, NN, MM, V>, sqp_schur_kernel<Model, P, S, V> — V the variant flags SQP_* of pmpc_sqp.hpp.
+// Launcher: sqp_launch_dev checks the request, then plan_schur → plan_reg (plan_extra_grids) → plan_generic fill one SqpPlan (kernel, LDS, redo step, route)
+// and launch_sqp_plan launches it.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdlib>
@@ -69,7 +72,7 @@ template <class Model> __host__ __device__ inline size_t big_scratch_doubles(int
 // KHBM: large-instance mode of the LDS-resident kernels — the KKT factor lives in an HBM workspace (Kws). A compile-time flag so
 // that in the normal mode every QP pointer provably addresses LDS (ds_read / ds_write instead of flat accesses, which cost the
 // LDS path most of its time when the location of K was a run-time choice)
-template <class Model, int NN = 0, int MM = 0, bool PROF = false, int HU = 0, bool KHBM = false, bool W2 = false, bool POL = false, bool CND = false, bool WG4 = false>   // WG4: the HBM-factor kernel on a workgroup of FOUR wavefronts per instance (BigTeam, pmpc_qp_big.hpp: small batches / lone instances); CND: condensed register QP (pmpc_qp_cond.hpp); W2: the HBM-factor kernel compiled for two wavefronts per SIMD (256 registers); POL: register-resident kernel with the Ruiz / filter-line-search hooks compiled in
+template <class Model, int NN = 0, int MM = 0, unsigned V = 0>   // V: the variant flags SQP_* (pmpc_sqp.hpp)
 #ifndef PMPC_SQP_WAVES
 #define PMPC_SQP_WAVES 2
 #endif
@@ -79,7 +82,7 @@ template <class Model, int NN = 0, int MM = 0, bool PROF = false, int HU = 0, bo
 #ifndef PMPC_COND1_WAVES
 #define PMPC_COND1_WAVES 1   /* condensed register kernel on at most 64 variables: wavefronts per SIMD — measured on the 11-node robot grid: two wavefronts (256 registers: 240 spilled values, eight scratch accesses in the ADMM loop) 2.82 ms per 4096, one wavefront 2.67 (the full inverse: 4.04) */
 #endif
-__global__ __launch_bounds__(WG4 ? 256 : 64, ((NN > 0 && NN + MM <= 64) ? PMPC_SQP_WAVES : ((NN > 0 && CND && NN <= 64) ? PMPC_COND1_WAVES : ((KHBM && W2) ? 2 : (KHBM ? PMPC_BIG_WAVES : 1))))) void sqp_kernel(Model model, const ChebData* __restrict__ cd, int B,
+__global__ __launch_bounds__((V & SQP_TEAM4) ? 256 : 64, ((NN > 0 && NN + MM <= 64) ? PMPC_SQP_WAVES : ((NN > 0 && (V & SQP_COND) && NN <= 64) ? PMPC_COND1_WAVES : (((V & SQP_HBM) && (V & SQP_TWO_WAVES)) ? 2 : ((V & SQP_HBM) ? PMPC_BIG_WAVES : 1))))) void sqp_kernel(Model model, const ChebData* __restrict__ cd, int B,
                                                  const double* __restrict__ x_guess, const double* __restrict__ lam_guess,
                                                  const double* __restrict__ d, const double* __restrict__ lbx,
                                                  const double* __restrict__ ubx, const double* __restrict__ lbg,
@@ -87,6 +90,8 @@ __global__ __launch_bounds__(WG4 ? 256 : 64, ((NN > 0 && NN + MM <= 64) ? PMPC_S
                                                  double* __restrict__ Hws, double* __restrict__ Aws, double* __restrict__ x,
                                                  double* __restrict__ lam, pmpc_sqp_info* __restrict__ info, unsigned long long* __restrict__ phase_cycles,
                                                  double* __restrict__ Kws, int it_begin, int it_end, double* __restrict__ slice_state, unsigned lds_dyn_doubles) {
+    static_assert(sqp_variant_ok<NN, V>(), "sqp_kernel: variant flags that no launcher route selects");
+    constexpr bool PROF = (V & SQP_PROF) != 0, KHBM = (V & SQP_HBM) != 0, POL = (V & SQP_HOOKS) != 0, CND = (V & SQP_COND) != 0, WG4 = (V & SQP_TEAM4) != 0;
     extern __shared__ double smem[];
     const size_t lds_doubles_total = __builtin_amdgcn_groupstaticsize() / sizeof(double) + lds_dyn_doubles;
     const int b = blockIdx.x;
@@ -201,7 +206,7 @@ __global__ __launch_bounds__(WG4 ? 256 : 64, ((NN > 0 && NN + MM <= 64) ? PMPC_S
     // stacked workspace K0 = [H ; J] ((n+m) x n, column-major, leading dimension n+m): lane i reads row i of K0 with ONE stride
     double* K0 = Hws + (size_t)b * (size_t)(n + m) * n;
     (void)Aws;
-    SqpDevice<Model, NN, MM, PROF, HU, KHBM, POL, CND ? -1 : ((KHBM && WG4) ? -3 : ((KHBM && W2) ? -2 : 0))> sqp(ocp, v, qw, K0, K0 + n, ss, qs);   // (W2 && WG4: the team kernel built for 256 registers — two workgroups per CU)
+    SqpDevice<Model, NN, MM, V> sqp(ocp, v, qw, K0, K0 + n, ss, qs);
     sqp.big_mail = big_mail;
     sqp.filt = filt;
     sqp.eig = eigw;
@@ -249,12 +254,14 @@ template <class Model, int PP, int SS> inline size_t sqp_schur_lds_bytes(bool po
     if (stage < need) stage = need;
     return ((size_t)(2 * dm.n + dm.m) + SqpLds::doubles(dm.n, dm.m, dm.mi) + stage + schur_lds_doubles_ct<Model, PP, SS>() + (Model::ND > 0 ? Model::ND : 1) + (pol ? FILTER_LDS_DOUBLES : 0) + 2) * sizeof(double);
 }
-template <class Model, int PP, int SS, bool PROF = false, bool POL = false>   // POL: with the filter line search (line_search = 1, LSFilter carried in LDS) — the hook of the reference's tests this kernel family carries
+template <class Model, int PP, int SS, unsigned V = 0>   // V: SQP_PROF, SQP_HOOKS (POL: with the filter line search, line_search = 1, LSFilter carried in LDS — the hook of the reference's tests this kernel family carries)
 __global__ __launch_bounds__(64, (SchurDims<Model, PP, SS>::N + SchurDims<Model, PP, SS>::M <= 64) ? PMPC_SQP_WAVES : 1)
 void sqp_schur_kernel(Model model, const ChebData* __restrict__ cd, int B, const double* __restrict__ x_guess, const double* __restrict__ lam_guess,
                       const double* __restrict__ d, const double* __restrict__ lbx, const double* __restrict__ ubx, pmpc_sqp_settings ss,
                       pmpc_qp_settings qs, double* __restrict__ x, double* __restrict__ lam, pmpc_sqp_info* __restrict__ info,
                       unsigned long long* __restrict__ phase_cycles) {
+    static_assert((V & ~(SQP_PROF | SQP_HOOKS)) == 0, "sqp_schur_kernel: phase timers and the line-search hook are its only variants");
+    constexpr bool PROF = (V & SQP_PROF) != 0, POL = (V & SQP_HOOKS) != 0;
     using SD = SchurDims<Model, PP, SS>;
     extern __shared__ double smem[];
     const int b = blockIdx.x;
@@ -293,7 +300,7 @@ void sqp_schur_kernel(Model model, const ChebData* __restrict__ cd, int B, const
     }
     for (int i = ln; i < m + n; i += WAVE) v.lam[i] = lam_guess ? lam_guess[(size_t)b * (m + n) + i] : 0.0;
     wsync();
-    SqpDevice<Model, n, m, PROF, 1, false, POL, PP * 256 + SS> sqp(ocp, v, qw, nullptr, nullptr, ss, qs);
+    SqpDevice<Model, n, m, V | SQP_BLOCK_BFGS, PP * 256 + SS> sqp(ocp, v, qw, nullptr, nullptr, ss, qs);
     sqp.filt = filt;
     sqp.hblk = hblk; sqp.hbrd = hbrd; sqp.qblk = qblk; sqp.xsc = xsc; sqp.dsc = dsc; sqp.dtab = dtab;
     schur_build_tables<Model, PP, SS>(ocp.s.D, dtab);
@@ -321,7 +328,7 @@ void sqp_schur_kernel(Model model, const ChebData* __restrict__ cd, int B, const
 // asks for the reference's full KKT form and keeps the dense kernels)
 inline bool schur_request_ok(const pmpc_sqp_settings* ss, const pmpc_qp_settings* qs, int slice_iters) {
     return (ss->hessian_update == 1 || ss->exact_hessian_every_iter) && (ss->regularisation == 0 || ss->regularisation == 2) && ss->preconditioner == 0 &&
-           ss->qp_solver == 0 && (ss->kkt_form == 0 || ss->kkt_form == 2) && qs->linear_solver == 0 && slice_iters == 0;   // (line_search = 1: the grids compiled with the hook, try_launch_schur)
+           ss->qp_solver == 0 && (ss->kkt_form == 0 || ss->kkt_form == 2) && qs->linear_solver == 0 && slice_iters == 0;   // (line_search = 1: the grids compiled with the hook, plan_schur)
 }
 // The per-call arguments of a fused SQP launch (device buffers, settings, context services), passed by const reference to the launch helpers;
 // the kernels still take their own by-value arguments
@@ -338,37 +345,6 @@ template <class Kernel> inline bool set_lds_attr(Kernel kern, size_t lds) {
     return hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess;
 }
 inline pmpc_status launch_status() { return (hipGetLastError() == hipSuccess) ? PMPC_OK : PMPC_ERR_HIP; }
-
-template <class Model, int PP, int SS>
-inline bool try_launch_schur(pmpc_context* ctx, const SqpArgs<Model>& a, pmpc_status* st) {
-    if (a.P != PP || a.S != SS) return false;
-    // Systems of at most 64 KKT rows stay on the one-row-per-lane dense kernel: its ADMM iteration is ONE register mat-vec (600 cycles), the
-    // block-structured one a chain of eight LDS exchanges and two mat-vecs (3.7 k cycles on config A) — measured 1.69 against 1.16 ms per 4096
-    // config-A instances although the factorisation is three times cheaper (DESIGN.md §6). PMPC_SCHUR_SMALL=1: developer switch.
-    if (SchurDims<Model, PP, SS>::N + SchurDims<Model, PP, SS>::M <= WAVE && !pmpc_internal_switch(ctx, PMPC_SW_SCHUR_SMALL)) return false;
-    const size_t lds = sqp_schur_lds_bytes<Model, PP, SS>(a.ss->line_search == 1);
-    if (lds > a.lds_limit) return false;
-    unsigned long long* phase = a.phase;
-    auto kern = sqp_schur_kernel<Model, PP, SS, false>;
-    if constexpr (SchurDims<Model, PP, SS>::NPAR == 0) { if (phase) kern = sqp_schur_kernel<Model, PP, SS, true>; }   // (no phase-timer build of the bordered form: a developer switch already)
-    else phase = nullptr;
-    // the filter line search (round 5): compiled for the grids of the reference's own tests with more than 64 KKT rows (11 and 16 nodes), no phase timers
-    if (a.ss->line_search == 1) {
-        if constexpr (SchurDims<Model, PP, SS>::NPAR == 0 && (SchurDims<Model, PP, SS>::NNODES == 11 || SchurDims<Model, PP, SS>::NNODES == 16)) { kern = sqp_schur_kernel<Model, PP, SS, false, true>; phase = nullptr; }
-        else return false;
-    }
-    if (!set_lds_attr(kern, lds)) { *st = PMPC_ERR_HIP; return true; }
-    pmpc_internal_set_route(ctx, PMPC_ROUTE_SCHUR);
-    hipLaunchKernelGGL(kern, dim3(a.B), dim3(WAVE), lds, a.stream, a.mdl, a.cd, a.B, a.x_guess, a.lam_guess, a.d, a.lbx, a.ubx, *a.ss, *a.qs, a.x, a.lam, a.info, phase);
-    *st = launch_status();
-    return true;
-}
-// the grids with a block-structured specialisation, per model (defined in the model's own translation unit: pmpc_schur_*.hip)
-template <class Model> struct SCHUR_GRIDS { static constexpr bool value = false; };
-template <> struct SCHUR_GRIDS<RobotOCP> { static constexpr bool value = true; };
-template <> struct SCHUR_GRIDS<CstrOCP> { static constexpr bool value = true; };
-template <> struct SCHUR_GRIDS<ParkingOCP> { static constexpr bool value = true; };   // (NP = 1: the bordered form, round 5)
-template <class Model> bool try_launch_schur_grids(pmpc_context* ctx, const SqpArgs<Model>& a, pmpc_status* st);
 
 // ---------------------------------------------------------------------------------------------------------------------------------------------
 // Round-robin execution of a batch that exceeds the resident wavefronts (register-resident QP, one KKT row per lane) — a DEVELOPER SWITCH
@@ -421,7 +397,7 @@ __global__ __launch_bounds__(256) void sqp_rr_init_kernel(int* __restrict__ queu
     }
 }
 
-template <class Model, int NN, int MM, int HU>
+template <class Model, int NN, int MM, unsigned V>   // V: SQP_BLOCK_BFGS or nothing
 __global__ __launch_bounds__(64, PMPC_SQP_WAVES) void sqp_kernel_rr(Model model, const ChebData* __restrict__ cd, int B,
                                                  const double* __restrict__ x_guess, const double* __restrict__ lam_guess,
                                                  const double* __restrict__ d, const double* __restrict__ lbx,
@@ -429,7 +405,7 @@ __global__ __launch_bounds__(64, PMPC_SQP_WAVES) void sqp_kernel_rr(Model model,
                                                  const double* __restrict__ ubg, pmpc_sqp_settings ss, pmpc_qp_settings qs,
                                                  double* __restrict__ Hws, double* __restrict__ x, double* __restrict__ lam, pmpc_sqp_info* __restrict__ info,
                                                  double* __restrict__ slice_state, int* __restrict__ queue, unsigned lds_dyn_doubles, unsigned long long* __restrict__ prof) {
-    static_assert(NN > 0 && NN + MM <= WAVE, "round-robin execution exists for the one-row-per-lane register path");
+    static_assert(NN > 0 && NN + MM <= WAVE && (V & ~SQP_BLOCK_BFGS) == 0, "round-robin execution exists for the one-row-per-lane register path, default hooks");
     extern __shared__ double smem[];
     const int P = cd->P, S = cd->S;
     Ocp<Model> ocp(model, P, S, cd->t_scale);
@@ -512,7 +488,7 @@ __global__ __launch_bounds__(64, PMPC_SQP_WAVES) void sqp_kernel_rr(Model model,
         int done_iters = pass;
         if (gave_up) { si.iter = 0; si.qp_solver_iter = 0; si.status = PMPC_SQP_REDO; si.flags = PMPC_FLAG_ILLCOND; si.primal_norm = 0.0; si.dual_norm = 0.0; si.max_violation = 0.0; si.cost = 0.0; }
         else {
-            SqpDevice<Model, NN, MM, false, HU, false> sqp(ocp, v, qw, K0, K0 + n, ss, qs);
+            SqpDevice<Model, NN, MM, V> sqp(ocp, v, qw, K0, K0 + n, ss, qs);
             sqp.filt = nullptr;
             sqp.eig = nullptr;
             sqp.trace = ss.iteration_trace ? ss.iteration_trace + (size_t)b * (size_t)ss.iteration_trace_capacity * PMPC_TRACE_DOUBLES : nullptr;
@@ -664,11 +640,15 @@ template <> struct LDS_PATH_PROFILED<KiteStandInOCP> { static constexpr bool val
 #ifndef PMPC_EXPERIMENT_COND_SMALL
 #define PMPC_EXPERIMENT_COND_SMALL 0
 #endif
-// Launch plan of the fused SQP kernel: the route a selection function (plan_reg, sqp_launch_dev) decided on, launched by launch_sqp_plan
-template <class Model> using SqpKernel = decltype(&sqp_kernel<Model>);   // (every instantiation of sqp_kernel / sqp_kernel_rr shares one function type)
+// Launch plan of the fused SQP kernel: the route a selection function (plan_schur, plan_reg, plan_generic) decided on, launched by launch_sqp_plan
+template <class Model> using SqpKernel = decltype(&sqp_kernel<Model>);   // (every instantiation of sqp_kernel shares one function type, and so do those of sqp_kernel_rr and of sqp_schur_kernel)
+// (the last one spelled out: naming an instantiation of sqp_schur_kernel would evaluate SchurDims, which exists only for the models that kernel serves)
+template <class Model> using SqpSchurKernel = void (*)(Model, const ChebData*, int, const double*, const double*, const double*, const double*, const double*, pmpc_sqp_settings,
+                                                       pmpc_qp_settings, double*, double*, pmpc_sqp_info*, unsigned long long*);
 template <class Model> struct SqpPlan {
     int route = PMPC_ROUTE_NONE;   // recorded for pmpc_sqp_last_route
     SqpKernel<Model> kern = nullptr;
+    SqpSchurKernel<Model> schur = nullptr;   // the block-structured kernel in place of `kern` (one launch for the whole solve)
     size_t lds = 0;                // dynamic LDS bytes
     unsigned threads = WAVE;       // 4 * WAVE: the four-wavefront team kernel
     bool timed = false;            // the phase timers are passed
@@ -699,8 +679,10 @@ template <class Model> inline pmpc_status launch_sqp_plan(pmpc_context* ctx, con
     const pmpc_sqp_settings& ss = *a.ss;
     unsigned long long* phase = p.timed ? a.phase : nullptr;
     pmpc_internal_set_route(ctx, p.route);
-    if (!set_lds_attr(p.kern, p.lds)) return PMPC_ERR_HIP;
-    if (p.rr) {   // one SQP iteration per work item, round-robin over the instances (sqp_kernel_rr), then the resume-mode launch for whatever is left in progress
+    if (!(p.schur ? set_lds_attr(p.schur, p.lds) : set_lds_attr(p.kern, p.lds))) return PMPC_ERR_HIP;
+    if (p.schur) {
+        hipLaunchKernelGGL(p.schur, dim3(a.B), dim3(WAVE), p.lds, a.stream, a.mdl, a.cd, a.B, a.x_guess, a.lam_guess, a.d, a.lbx, a.ubx, ss, *a.qs, a.x, a.lam, a.info, phase);
+    } else if (p.rr) {   // one SQP iteration per work item, round-robin over the instances (sqp_kernel_rr), then the resume-mode launch for whatever is left in progress
         if (!set_lds_attr(p.rr, p.lds)) return PMPC_ERR_HIP;
         int* queue = (int*)(a.slice_state + (size_t)a.B * 2 * OcpDims<Model>(a.P, a.S).n);   // behind the slice state (sqp_launch_dev sizes the workspace for it)
         const size_t words = (size_t)a.B * ss.max_iter > (size_t)RR_HEADER_WORDS ? (size_t)a.B * ss.max_iter : (size_t)RR_HEADER_WORDS;
@@ -726,6 +708,34 @@ template <class Model> inline void plan_redo_lds(pmpc_context* ctx, const SqpArg
     if (lds > a.lds_limit) return;
     p.redo = sqp_kernel<Model>; p.redo_lds = lds; p.redo_full_form = true;
 }
+// Block-structured kernel on the grid (PP, SS); false: another grid, or this one has no block-structured kernel for the request
+template <class Model, int PP, int SS>
+inline bool plan_schur(pmpc_context* ctx, const SqpArgs<Model>& a, SqpPlan<Model>& p) {
+    using SD = SchurDims<Model, PP, SS>;
+    if (a.P != PP || a.S != SS) return false;
+    // Systems of at most 64 KKT rows stay on the one-row-per-lane dense kernel: its ADMM iteration is ONE register mat-vec (600 cycles), the
+    // block-structured one a chain of eight LDS exchanges and two mat-vecs (3.7 k cycles on config A) — measured 1.69 against 1.16 ms per 4096
+    // config-A instances although the factorisation is three times cheaper (DESIGN.md §6). PMPC_SCHUR_SMALL=1: developer switch.
+    if (SD::N + SD::M <= WAVE && !pmpc_internal_switch(ctx, PMPC_SW_SCHUR_SMALL)) return false;
+    const size_t lds = sqp_schur_lds_bytes<Model, PP, SS>(a.ss->line_search == 1);
+    if (lds > a.lds_limit) return false;
+    SqpSchurKernel<Model> kern = sqp_schur_kernel<Model, PP, SS>; bool timed = false;
+    if constexpr (SD::NPAR == 0) { if (a.phase) { kern = sqp_schur_kernel<Model, PP, SS, SQP_PROF>; timed = true; } }   // (no phase-timer build of the bordered form: a developer switch already)
+    // the filter line search (round 5): compiled for the grids of the reference's own tests with more than 64 KKT rows (11 and 16 nodes), no phase timers
+    if (a.ss->line_search == 1) {
+        if constexpr (SD::NPAR == 0 && (SD::NNODES == 11 || SD::NNODES == 16)) { kern = sqp_schur_kernel<Model, PP, SS, SQP_HOOKS>; timed = false; }
+        else return false;
+    }
+    p.route = PMPC_ROUTE_SCHUR; p.schur = kern; p.lds = lds; p.timed = timed;   // (the redo step: sqp_launch_dev — this function is compiled in pmpc_schur_*.hip, which do not carry the LDS-resident kernel)
+    return true;
+}
+// the grids with a block-structured specialisation, per model (defined in the model's own translation unit: pmpc_schur_*.hip)
+template <class Model> struct SCHUR_GRIDS { static constexpr bool value = false; };
+template <> struct SCHUR_GRIDS<RobotOCP> { static constexpr bool value = true; };
+template <> struct SCHUR_GRIDS<CstrOCP> { static constexpr bool value = true; };
+template <> struct SCHUR_GRIDS<ParkingOCP> { static constexpr bool value = true; };   // (NP = 1: the bordered form, round 5)
+template <class Model> bool plan_schur_grids(pmpc_context* ctx, const SqpArgs<Model>& a, SqpPlan<Model>& p);
+
 template <class Model, int NN_, int MM_> struct COND_REG_OK { static constexpr bool value = NN_ + MM_ > WAVE && NN_ <= 112 && MM_ > 0 && MM_ <= WAVE && Model::NP <= 1; };   // (NP = 1 and NG > 0 since round 6: the parameter's dense column of A as a wave reduction, the path-constraint rows as own-node blocks without a D~ row)
 // Register-resident QP specialisations are selected from the compile-time model dimensions and the runtime node count: one KKT row per lane up to
 // 64 rows, two rows per lane up to 128 (the Hessian-update policy is a run-time choice there); false: this grid has no register kernel for the request.
@@ -750,13 +760,13 @@ inline bool plan_reg(pmpc_context* ctx, const SqpArgs<Model>& a, SqpPlan<Model>&
         if (ONE_ROW && LEAN && (ss->hessian_update == 1 || a.phase)) return false;
         // the full-inverse kernel
         p.route = ONE_ROW ? PMPC_ROUTE_REG1 : PMPC_ROUTE_REG2;
-        p.kern = sqp_kernel<Model, NN_, MM_, false>;
+        p.kern = sqp_kernel<Model, NN_, MM_>;
         p.lds = lds_full;
         if constexpr (ONE_ROW) {
             p.timed = true;
             if constexpr (!LEAN)
-                p.kern = (ss->hessian_update == 1) ? sqp_kernel<Model, NN_, MM_, false, 1>   // (no phase timers in the block-BFGS specialisation)
-                                                   : (a.phase ? sqp_kernel<Model, NN_, MM_, true> : sqp_kernel<Model, NN_, MM_, false>);
+                p.kern = (ss->hessian_update == 1) ? sqp_kernel<Model, NN_, MM_, SQP_BLOCK_BFGS>   // (no phase timers in the block-BFGS specialisation)
+                                                   : (a.phase ? sqp_kernel<Model, NN_, MM_, SQP_PROF> : sqp_kernel<Model, NN_, MM_>);
             plan_redo_lds(ctx, a, p);
             if constexpr (!LEAN) {   // more instances than resident wavefronts: one SQP iteration per work item (PMPC_SQP_RR=1, sqp_kernel_rr)
 #ifdef PMPC_RR_PROFILE
@@ -767,12 +777,12 @@ inline bool plan_reg(pmpc_context* ctx, const SqpArgs<Model>& a, SqpPlan<Model>&
                 const int slots = PMPC_SQP_WAVES * pmpc_internal_simd_count(ctx);
                 if (!pol && a.slice_state && a.slice_iters == 0 && rr_phase_ok && ss->max_iter > 1 && ss->max_iter <= RR_MAX_ITER && a.B > slots && a.B <= RR_MAX_BATCH &&
                     (size_t)a.B * ss->max_iter < ((size_t)1 << 30) && pmpc_internal_sqp_rr(ctx)) {
-                    p.rr = (ss->hessian_update == 1) ? sqp_kernel_rr<Model, NN_, MM_, 1> : sqp_kernel_rr<Model, NN_, MM_, 0>;
+                    p.rr = (ss->hessian_update == 1) ? sqp_kernel_rr<Model, NN_, MM_, SQP_BLOCK_BFGS> : sqp_kernel_rr<Model, NN_, MM_, 0>;
                     p.rr_init = sqp_rr_init_kernel<Model>;
                 }
             }
         } else if constexpr (LDS_PATH_PROFILED<Model>::value && !LEAN) {   // developer builds with phase timers
-            if (a.phase && !pol) { p.kern = sqp_kernel<Model, NN_, MM_, true>; p.timed = true; }
+            if (a.phase && !pol) { p.kern = sqp_kernel<Model, NN_, MM_, SQP_PROF>; p.timed = true; }
         }
         // condensed override (pmpc_qp_cond.hpp): the condensed register QP; kkt_form = 1 keeps the full inverse, which serves the redo launch behind it
         const bool condreg = ss->kkt_form == 0 && !pmpc_internal_switch(ctx, PMPC_SW_NO_CONDREG);
@@ -783,7 +793,7 @@ inline bool plan_reg(pmpc_context* ctx, const SqpArgs<Model>& a, SqpPlan<Model>&
 #if PMPC_EXPERIMENT_COND_SMALL   /* developer experiment (round 6, EXPERIMENTS.md): the CONDENSED register QP on a grid of at most 64 KKT rows — config A on 35 instead of 56 rows; the redo stays on the LDS-resident kernel */
         if constexpr (ONE_ROW && !LEAN && NNODES == 7 && Model::NP == 0 && Model::NG == 0) {
             if (!pol && condreg && ss->hessian_update == 0 && !a.phase) {
-                p.route = PMPC_ROUTE_CONDREG; p.kern = sqp_kernel<Model, NN_, MM_, false, 0, false, false, false, true>; p.rr = nullptr;
+                p.route = PMPC_ROUTE_CONDREG; p.kern = sqp_kernel<Model, NN_, MM_, SQP_COND>; p.rr = nullptr;
                 p.lds = sqp_kernel_lds_bytes<Model>(a.P, a.S, SqpLdsLayout::Cond1);
             }
         }
@@ -794,16 +804,16 @@ inline bool plan_reg(pmpc_context* ctx, const SqpArgs<Model>& a, SqpPlan<Model>&
                 if constexpr (NN_ <= WAVE) lds = sqp_kernel_lds_bytes<Model>(a.P, a.S, SqpLdsLayout::Cond1);   // (two wavefronts per SIMD: a smaller staging lets more instances share a CU)
                 else lds = sqp_kernel_lds_bytes<Model>(a.P, a.S, SqpLdsLayout::Cond2, 0, false, (size_t)cond_qp_staging<NN_, MM_, NNODES>());   // (its own tile set's staging, not the full inverse's: four instead of three instances per CU on the 16-node grid)
                 bool timed = false;
-                auto kern = sqp_kernel<Model, NN_, MM_, false, 0, false, false, false, true>;
-                if constexpr (LDS_PATH_PROFILED<Model>::value && !LEAN) { if (a.phase) { kern = sqp_kernel<Model, NN_, MM_, true, 0, false, false, false, true>; timed = true; } }
-                condensed(kern, lds, timed, sqp_kernel<Model, NN_, MM_, false>);
+                auto kern = sqp_kernel<Model, NN_, MM_, SQP_COND>;
+                if constexpr (LDS_PATH_PROFILED<Model>::value && !LEAN) { if (a.phase) { kern = sqp_kernel<Model, NN_, MM_, SQP_PROF | SQP_COND>; timed = true; } }
+                condensed(kern, lds, timed, sqp_kernel<Model, NN_, MM_>);
             }
         }
         // hook override: the builds with the policy hooks compiled in (POL)
         if constexpr (POLK) {
             if (pol) {
-                p.kern = sqp_kernel<Model, NN_, MM_, false, 0, false, false, true>;
-                if constexpr (ONE_ROW) { if (ss->hessian_update == 1) p.kern = sqp_kernel<Model, NN_, MM_, false, 1, false, false, true>; }
+                p.kern = sqp_kernel<Model, NN_, MM_, SQP_HOOKS>;
+                if constexpr (ONE_ROW) { if (ss->hessian_update == 1) p.kern = sqp_kernel<Model, NN_, MM_, SQP_BLOCK_BFGS | SQP_HOOKS>; }
                 const SqpKernel<Model> full = p.kern;
                 // the hooks keep the condensed QP — the filter line search and eigenvalue mirroring since rounds 4 / 6, the Ruiz preconditioner since late round 6: it rescales the
                 // workspace, so the hook builds read their D~ tables (one set per state index) and, after an equilibration, the node blocks back from it (pmpc_qp_cond.hpp WS)
@@ -811,7 +821,7 @@ inline bool plan_reg(pmpc_context* ctx, const SqpArgs<Model>& a, SqpPlan<Model>&
                     if (condreg && !(ss->preconditioner == 1 && pmpc_internal_switch(ctx, PMPC_SW_NO_CONDREG_RUIZ))) {
                         const size_t stg = ss->preconditioner == 1 ? (size_t)cond_qp_staging_ws<NN_, MM_, NNODES, Model::NX>() : (size_t)cond_qp_staging<NN_, MM_, NNODES>();   // (the tables per state index only with the Ruiz preconditioner: the other hooks keep the smaller staging — more instances per CU)
                         const size_t lds = sqp_kernel_lds_bytes<Model>(a.P, a.S, SqpLdsLayout::Cond2, 0, true, stg) + sqp_eig_lds_bytes<Model>(a.P, a.S, ss);
-                        if (lds <= a.lds_limit) condensed(sqp_kernel<Model, NN_, MM_, false, 0, false, false, true, true>, lds, false, full);
+                        if (lds <= a.lds_limit) condensed(sqp_kernel<Model, NN_, MM_, SQP_HOOKS | SQP_COND>, lds, false, full);
                     }
                 }
             }
@@ -829,6 +839,75 @@ template <> struct EXTRA_GRIDS<ParkingOCP> { static constexpr bool value = true;
 template <> struct EXTRA_GRIDS<RobotNGOCP> { static constexpr bool value = true; };
 template <> struct EXTRA_GRIDS<ParkingNGOCP> { static constexpr bool value = true; };
 template <class Model> bool plan_extra_grids(pmpc_context* ctx, const SqpArgs<Model>& a, SqpPlan<Model>& p);
+
+// The size-generic kernels, for whatever no specialisation took: LDS-resident factor, HBM-resident factor (with the larger workspace from a second services
+// call), its two-wavefronts-per-SIMD build or the team of four wavefronts. A status other than PMPC_OK: the request fits none of them / the workspace failed.
+template <class Model>
+inline pmpc_status plan_generic(pmpc_context* ctx, SqpArgs<Model>& a, SqpPlan<Model>& plan, double t0, double tf, size_t base, int force_lds) {
+    const int P = a.P, S = a.S, B = a.B, slice_iters = a.slice_iters;
+    const pmpc_sqp_settings* ss = a.ss; const pmpc_qp_settings* qs = a.qs; const size_t lds_limit = a.lds_limit; OcpDims<Model> dm(P, S);
+    size_t lds = sqp_kernel_lds_bytes<Model>(P, S, SqpLdsLayout::LdsFactor, ss->qp_solver) + sqp_eig_lds_bytes<Model>(P, S, ss);
+    if (lds > lds_limit && ss->qp_solver == 1) return PMPC_ERR_UNSUPPORTED_SIZE;   // the stacked system lives in LDS only
+    if (lds > lds_limit && qs->linear_solver == 1) return PMPC_ERR_UNSUPPORTED_SIZE;   // the pivoted factorisation lives in LDS only
+    // Above BIG_KKT_MIN_ROWS rows the blocked tile factorisation (fp64 MFMA trailing updates, factor panels streamed from HBM / L2, 13 KB of LDS:
+    // one instance per SIMD) beats the LDS-resident triangle, whose footprint leaves one or two instances per CU — measured on robot grids, 2048
+    // instances: 104 rows 21.0 -> 18.3 ms, 128 rows (the reference's mpc_wrapper_test grid) 52.2 -> 25.3, 168 rows 247.6 -> 39.4; 72 rows 13.5 -> 17.7
+    // (stays in LDS). The stacked OSQP-form system and the pivoted factorisation exist in LDS only.
+    const bool prefer_big = dm.n + dm.m >= BIG_KKT_MIN_ROWS && ss->qp_solver == 0 && qs->linear_solver == 0 && !force_lds;
+    if (lds > lds_limit || prefer_big) {   // large instance: KKT factor in HBM, SQP / QP vectors in an HBM scratch behind it
+        lds = sqp_kernel_lds_bytes<Model>(P, S, SqpLdsLayout::HbmFactor) + sqp_eig_lds_bytes<Model>(P, S, ss);
+        if (lds > lds_limit) return PMPC_ERR_UNSUPPORTED_SIZE;
+        const size_t base16 = (base + 1) & ~(size_t)1;   // (16-byte boundary for the factor workspaces)
+        const void* cdv = nullptr; double* ws = nullptr; void* streamv = nullptr;
+        const pmpc_status st = pmpc_internal_services(ctx, P, S, t0, tf, (base16 + (size_t)B * (BigKkt::doubles(dm.n + dm.m) + big_scratch_doubles<Model>(P, S))) * sizeof(double), &cdv, &ws, &streamv,
+                                                      &a.lds_limit, &a.phase, &force_lds);
+        if (st != PMPC_OK) return st;
+        a.Hws = ws; a.Aws = ws + (size_t)B * dm.n * dm.n; a.slice_state = a.Aws + (size_t)B * dm.m * dm.n; plan.Kws = ws + base16;
+    }
+    unsigned long long* const phase = a.phase;
+    const bool hbm = plan.Kws != nullptr;
+    plan.route = hbm ? PMPC_ROUTE_HBM : PMPC_ROUTE_LDS;
+    plan.lds = lds;
+    plan.timed = true;
+    plan.kern = hbm ? sqp_kernel<Model, 0, 0, SQP_HBM> : sqp_kernel<Model>;
+    // Mid-size instances on the HBM-factor kernel stream little per wavefront: with more instances than SIMDs a second wavefront per SIMD (a 256-register
+    // build of the same kernel) hides part of that latency — per 4096 robots 128 rows 40.5 -> 35.4 ms, 168 rows 64.3 -> 60.8; at config C's 464 rows
+    // the second wave only thrashes the L2 (2048 instances 93.0 -> 99.1 ms), hence the row bound.
+    if (hbm && dm.n + dm.m < BIG_TWO_WAVES_MAX_ROWS && B > pmpc_internal_simd_count(ctx) && !phase) plan.kern = sqp_kernel<Model, 0, 0, SQP_HBM | SQP_TWO_WAVES>;
+    // Small batches of large instances: a workgroup of four wavefronts per instance (BigTeam, pmpc_qp_big.hpp). With at most one instance per CU the chip is a
+    // quarter full at best on the one-wavefront kernel and the launch takes a lone instance's time; the team cuts that time (the condensed build, the blocked
+    // factorisation and the two triangular passes run on four SIMDs). Beyond BIG_WG4_MAX_BATCH instances the one-wavefront kernel's four instances per CU win.
+    // PMPC_BIG_WG4 = 0 / 1: developer switch (never / whenever eligible).
+    if constexpr (Model::NG == 0 && Model::NP == 0) {
+        const int wg4_on = pmpc_internal_switch(ctx, PMPC_SW_BIG_WG4_ON), wg4_off = pmpc_internal_switch(ctx, PMPC_SW_BIG_WG4_OFF);
+        const bool eligible = hbm && plan.kern == sqp_kernel<Model, 0, 0, SQP_HBM> && ss->kkt_form == 0 && ss->preconditioner == 0 && ss->qp_solver == 0 && ss->regularisation != 1 &&
+                              dm.n <= BIG_COND_MAX_ROWS && dm.m <= BIG_COND_MAX_ROWS && slice_iters == 0;
+        // Up to one instance per CU the team kernel may use the whole register file (512 per lane); from there to TWO instances per CU a second build of it,
+        // compiled for 256 registers so that two workgroups share a CU, still beats one wavefront per instance (kite-sized, 512 instances: 11.7 against 13.4 ms;
+        // the register diet costs it 4 % at 256 instances, hence two builds); beyond that the one-wavefront kernel's throughput wins (EXPERIMENTS.md round 5).
+        const int per_cu = BIG_WG4_MAX_BATCH * (pmpc_internal_simd_count(ctx) / 4) / 256;
+        const bool want = (wg4_on || wg4_off) ? (wg4_on != 0) : (B <= 2 * per_cu);
+        if (eligible && want) {
+            plan.kern = (B <= per_cu) ? sqp_kernel<Model, 0, 0, SQP_HBM | SQP_TEAM4> : sqp_kernel<Model, 0, 0, SQP_HBM | SQP_TWO_WAVES | SQP_TEAM4>;
+            plan.threads = 4 * WAVE;
+        }
+    }
+    const bool team_kernel = plan.threads != WAVE;
+    if constexpr (LDS_PATH_PROFILED<Model>::value) {   // developer builds with phase timers
+        if (phase) {
+            plan.kern = hbm ? sqp_kernel<Model, 0, 0, SQP_PROF | SQP_HBM> : sqp_kernel<Model, 0, 0, SQP_PROF>;
+            if constexpr (Model::NG == 0 && Model::NP == 0) { if (team_kernel) plan.kern = sqp_kernel<Model, 0, 0, SQP_PROF | SQP_HBM | SQP_TEAM4>; }
+        }
+    } else if (phase && team_kernel) { plan.kern = sqp_kernel<Model, 0, 0, SQP_HBM>; plan.threads = WAVE; }
+    if (hbm && ss->kkt_form == 0 && ss->qp_solver == 0 && !pmpc_internal_switch(ctx, PMPC_SW_NO_REDO_LAUNCH)) {
+        // redo launch (large-instance kernel, condensed mode): the instances whose QP gave up at its conditioning gate (PMPC_FLAG_ILLCOND; none on any
+        // BASELINE workload) are solved again, from their guesses, by the same kernel in the (n + m)-row KKT form
+        // (the two-wavefronts-per-SIMD build of the one-wavefront kernel: an instantiation of its own, so that a profile lists the redo launches — which
+        //  normally do nothing — on their own line instead of halving the large-instance kernel's averages; the full KKT form has no team version)
+        plan.redo = sqp_kernel<Model, 0, 0, SQP_HBM | SQP_TWO_WAVES>; plan.redo_lds = lds; plan.redo_full_form = true;
+    }
+    return PMPC_OK;
+}
 
 // Launch the fused SQP kernel for `Model` on DEVICE buffers (asynchronous on the context's stream): block-structured kernel → register grids → LDS / HBM-factor / team kernel.
 template <class Model>
@@ -854,92 +933,26 @@ inline pmpc_status sqp_launch_dev(pmpc_context* ctx, const Model& mdl, int P, in
     if (qs->linear_solver != 0 && qs->linear_solver != 1) return PMPC_ERR_INVALID_ARGUMENT;
     SqpArgs<Model> a{mdl, (const ChebData*)cdv, P, S, B, x_guess, lam_guess, d, lbx, ubx, lbg, ubg, x, lam, info, ss, qs,
                      ws, ws + (size_t)B * dm.n * dm.n, (hipStream_t)streamv, lds_limit, phase, ws + (size_t)B * dm.n * dm.n + (size_t)B * dm.m * dm.n, slice_iters};
+    SqpPlan<Model> plan;
+    bool planned = false;
     if constexpr (SCHUR_GRIDS<Model>::value) {   // block-diagonal Hessian on a grid with a block-structured kernel
         // (the redo launch behind this kernel's conditioning gate runs the LDS-resident kernel: a grid it does not fit — only under a developer's PMPC_LDS_LIMIT —
         //  keeps the dense kernels, so that an instance that gave up can always be solved again)
-        if (!force_lds && !pmpc_internal_switch(ctx, PMPC_SW_NO_SCHUR) && schur_request_ok(ss, qs, slice_iters) && sqp_kernel_lds_bytes<Model>(P, S, SqpLdsLayout::LdsFactor) <= lds_limit) {
-            pmpc_status rst = PMPC_OK;
-            if (try_launch_schur_grids<Model>(ctx, a, &rst)) {
-                // redo launch: the instances whose block-structured QP gave up at its conditioning gate (PMPC_SCHUR_COND_GATE; none on any BASELINE workload) are
-                // solved again, from their guesses, on the LDS-resident static LDL^T of the (n + m)-row matrix (every compiled grid fits)
-                SqpPlan<Model> redo;
-                if (rst == PMPC_OK) plan_redo_lds(ctx, a, redo);
-                if (rst == PMPC_OK && !launch_redo(redo, a)) rst = PMPC_ERR_HIP;
-                return rst;
-            }
-        }
+        if (!force_lds && !pmpc_internal_switch(ctx, PMPC_SW_NO_SCHUR) && schur_request_ok(ss, qs, slice_iters) && sqp_kernel_lds_bytes<Model>(P, S, SqpLdsLayout::LdsFactor) <= lds_limit)
+            planned = plan_schur_grids<Model>(ctx, a, plan);
+        // redo launch: the instances whose block-structured QP gave up at its conditioning gate (PMPC_SCHUR_COND_GATE; none on any BASELINE workload) are
+        // solved again, from their guesses, on the LDS-resident static LDL^T of the (n + m)-row matrix (every compiled grid fits)
+        if (planned) plan_redo_lds(ctx, a, plan);
     }
     // kkt_form = 2 asks for the block-structured range-space form where a specialisation is compiled (above); everywhere else it means the default
     pmpc_sqp_settings ss_default_form;
-    if (ss->kkt_form == 2) { ss_default_form = *ss; ss_default_form.kkt_form = 0; ss = a.ss = &ss_default_form; }
-    SqpPlan<Model> plan;
-    bool planned = false;
-    if (!force_lds && ss->qp_solver == 0 && qs->linear_solver == 0) {   // (preconditioner / line_search = 1: the 7- and 11-node register kernels carry them, see plan_reg)
+    if (!planned && ss->kkt_form == 2) { ss_default_form = *ss; ss_default_form.kkt_form = 0; ss = a.ss = &ss_default_form; }
+    if (!planned && !force_lds && ss->qp_solver == 0 && qs->linear_solver == 0) {   // (preconditioner / line_search = 1: the 7- and 11-node register kernels carry them, see plan_reg)
         // node counts whose KKT system can fit 64 rows for small models (7 nodes: config A / D); 11: config B / the reference's P = 5, S = 2 grids (88..110 KKT rows)
         planned = plan_reg<Model, 7>(ctx, a, plan) || plan_reg<Model, 5>(ctx, a, plan) || plan_reg<Model, 11>(ctx, a, plan);
         if constexpr (EXTRA_GRIDS<Model>::value) planned = planned || plan_extra_grids<Model>(ctx, a, plan);   // 3-, 4-, 6-, 8-, 9-, 10-, 12- and 13-node grids of the built-in models
     }
-    if (!planned) {
-        size_t lds = sqp_kernel_lds_bytes<Model>(P, S, SqpLdsLayout::LdsFactor, ss->qp_solver) + sqp_eig_lds_bytes<Model>(P, S, ss);
-        if (lds > lds_limit && ss->qp_solver == 1) return PMPC_ERR_UNSUPPORTED_SIZE;   // the stacked system lives in LDS only
-        if (lds > lds_limit && qs->linear_solver == 1) return PMPC_ERR_UNSUPPORTED_SIZE;   // the pivoted factorisation lives in LDS only
-        // Above BIG_KKT_MIN_ROWS rows the blocked tile factorisation (fp64 MFMA trailing updates, factor panels streamed from HBM / L2, 13 KB of LDS:
-        // one instance per SIMD) beats the LDS-resident triangle, whose footprint leaves one or two instances per CU — measured on robot grids, 2048
-        // instances: 104 rows 21.0 -> 18.3 ms, 128 rows (the reference's mpc_wrapper_test grid) 52.2 -> 25.3, 168 rows 247.6 -> 39.4; 72 rows 13.5 -> 17.7
-        // (stays in LDS). The stacked OSQP-form system and the pivoted factorisation exist in LDS only.
-        const bool prefer_big = dm.n + dm.m >= BIG_KKT_MIN_ROWS && ss->qp_solver == 0 && qs->linear_solver == 0 && !force_lds;
-        if (lds > lds_limit || prefer_big) {   // large instance: KKT factor in HBM, SQP / QP vectors in an HBM scratch behind it
-            lds = sqp_kernel_lds_bytes<Model>(P, S, SqpLdsLayout::HbmFactor) + sqp_eig_lds_bytes<Model>(P, S, ss);
-            if (lds > lds_limit) return PMPC_ERR_UNSUPPORTED_SIZE;
-            const size_t base16 = (base + 1) & ~(size_t)1;   // (16-byte boundary for the factor workspaces)
-            st = pmpc_internal_services(ctx, P, S, t0, tf, (base16 + (size_t)B * (BigKkt::doubles(dm.n + dm.m) + big_scratch_doubles<Model>(P, S))) * sizeof(double), &cdv, &ws, &streamv,
-                                        &a.lds_limit, &a.phase, &force_lds);
-            if (st != PMPC_OK) return st;
-            a.Hws = ws; a.Aws = ws + (size_t)B * dm.n * dm.n; a.slice_state = a.Aws + (size_t)B * dm.m * dm.n; plan.Kws = ws + base16;
-        }
-        phase = a.phase;
-        const bool hbm = plan.Kws != nullptr;
-        plan.route = hbm ? PMPC_ROUTE_HBM : PMPC_ROUTE_LDS;
-        plan.lds = lds;
-        plan.timed = true;
-        plan.kern = hbm ? sqp_kernel<Model, 0, 0, false, 0, true> : sqp_kernel<Model>;
-        // Mid-size instances on the HBM-factor kernel stream little per wavefront: with more instances than SIMDs a second wavefront per SIMD (a 256-register
-        // build of the same kernel) hides part of that latency — per 4096 robots 128 rows 40.5 -> 35.4 ms, 168 rows 64.3 -> 60.8; at config C's 464 rows
-        // the second wave only thrashes the L2 (2048 instances 93.0 -> 99.1 ms), hence the row bound.
-        if (hbm && dm.n + dm.m < BIG_TWO_WAVES_MAX_ROWS && B > pmpc_internal_simd_count(ctx) && !phase) plan.kern = sqp_kernel<Model, 0, 0, false, 0, true, true>;
-        // Small batches of large instances: a workgroup of four wavefronts per instance (BigTeam, pmpc_qp_big.hpp). With at most one instance per CU the chip is a
-        // quarter full at best on the one-wavefront kernel and the launch takes a lone instance's time; the team cuts that time (the condensed build, the blocked
-        // factorisation and the two triangular passes run on four SIMDs). Beyond BIG_WG4_MAX_BATCH instances the one-wavefront kernel's four instances per CU win.
-        // PMPC_BIG_WG4 = 0 / 1: developer switch (never / whenever eligible).
-        if constexpr (Model::NG == 0 && Model::NP == 0) {
-            const int wg4_on = pmpc_internal_switch(ctx, PMPC_SW_BIG_WG4_ON), wg4_off = pmpc_internal_switch(ctx, PMPC_SW_BIG_WG4_OFF);
-            const bool eligible = hbm && plan.kern == sqp_kernel<Model, 0, 0, false, 0, true> && ss->kkt_form == 0 && ss->preconditioner == 0 && ss->qp_solver == 0 && ss->regularisation != 1 &&
-                                  dm.n <= BIG_COND_MAX_ROWS && dm.m <= BIG_COND_MAX_ROWS && slice_iters == 0;
-            // Up to one instance per CU the team kernel may use the whole register file (512 per lane); from there to TWO instances per CU a second build of it,
-            // compiled for 256 registers so that two workgroups share a CU, still beats one wavefront per instance (kite-sized, 512 instances: 11.7 against 13.4 ms;
-            // the register diet costs it 4 % at 256 instances, hence two builds); beyond that the one-wavefront kernel's throughput wins (EXPERIMENTS.md round 5).
-            const int per_cu = BIG_WG4_MAX_BATCH * (pmpc_internal_simd_count(ctx) / 4) / 256;
-            const bool want = (wg4_on || wg4_off) ? (wg4_on != 0) : (B <= 2 * per_cu);
-            if (eligible && want) {
-                plan.kern = (B <= per_cu) ? sqp_kernel<Model, 0, 0, false, 0, true, false, false, false, true> : sqp_kernel<Model, 0, 0, false, 0, true, true, false, false, true>;
-                plan.threads = 4 * WAVE;
-            }
-        }
-        const bool team_kernel = plan.threads != WAVE;
-        if constexpr (LDS_PATH_PROFILED<Model>::value) {   // developer builds with phase timers
-            if (phase) {
-                plan.kern = hbm ? sqp_kernel<Model, 0, 0, true, 0, true> : sqp_kernel<Model, 0, 0, true>;
-                if constexpr (Model::NG == 0 && Model::NP == 0) { if (team_kernel) plan.kern = sqp_kernel<Model, 0, 0, true, 0, true, false, false, false, true>; }
-            }
-        } else if (phase && team_kernel) { plan.kern = sqp_kernel<Model, 0, 0, false, 0, true>; plan.threads = WAVE; }
-        if (hbm && ss->kkt_form == 0 && ss->qp_solver == 0 && !pmpc_internal_switch(ctx, PMPC_SW_NO_REDO_LAUNCH)) {
-            // redo launch (large-instance kernel, condensed mode): the instances whose QP gave up at its conditioning gate (PMPC_FLAG_ILLCOND; none on any
-            // BASELINE workload) are solved again, from their guesses, by the same kernel in the (n + m)-row KKT form
-            // (the two-wavefronts-per-SIMD build of the one-wavefront kernel: an instantiation of its own, so that a profile lists the redo launches — which
-            //  normally do nothing — on their own line instead of halving the large-instance kernel's averages; the full KKT form has no team version)
-            plan.redo = sqp_kernel<Model, 0, 0, false, 0, true, true>; plan.redo_lds = lds; plan.redo_full_form = true;
-        }
-    }
+    if (!planned) { st = plan_generic(ctx, a, plan, t0, tf, base, force_lds); if (st != PMPC_OK) return st; }
     return launch_sqp_plan(ctx, plan, a);
 }
 

@@ -5,6 +5,6 @@
 #include "pmpc_models.hpp"
 #include "pmpc_launch.hpp"
 
-#define PMPC_SCHUR_ARGS pmpc_context* ctx, const pmpc::SqpArgs<MODEL>& a, pmpc_status* st
-#define PMPC_SCHUR_TRY(PP, SS) \
-    if (pmpc::try_launch_schur<MODEL, PP, SS>(ctx, a, st)) return true;
+#define PMPC_SCHUR_ARGS pmpc_context* ctx, const pmpc::SqpArgs<MODEL>& a, pmpc::SqpPlan<MODEL>& p
+#define PMPC_SCHUR_PLAN(PP, SS) \
+    if (pmpc::plan_schur<MODEL, PP, SS>(ctx, a, p)) return true;

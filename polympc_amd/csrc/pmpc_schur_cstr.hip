@@ -2,9 +2,9 @@
 #include "pmpc_schur.hpp"
 #define MODEL pmpc::CstrOCP
 namespace pmpc {
-template <> bool try_launch_schur_grids<MODEL>(PMPC_SCHUR_ARGS) {
-    PMPC_SCHUR_TRY(5, 2)
-    PMPC_SCHUR_TRY(6, 1)
+template <> bool plan_schur_grids<MODEL>(PMPC_SCHUR_ARGS) {
+    PMPC_SCHUR_PLAN(5, 2)
+    PMPC_SCHUR_PLAN(6, 1)
     return false;
 }
 }  // namespace pmpc

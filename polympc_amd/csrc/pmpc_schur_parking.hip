@@ -8,9 +8,9 @@
 #include "pmpc_schur.hpp"
 #define MODEL pmpc::ParkingOCP
 namespace pmpc {
-template <> bool try_launch_schur_grids<MODEL>(PMPC_SCHUR_ARGS) {
+template <> bool plan_schur_grids<MODEL>(PMPC_SCHUR_ARGS) {
     if (a.ss->kkt_form != 2) return false;
-    PMPC_SCHUR_TRY(5, 2)
+    PMPC_SCHUR_PLAN(5, 2)
     return false;
 }
 }  // namespace pmpc

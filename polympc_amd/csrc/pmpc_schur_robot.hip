@@ -3,10 +3,10 @@
 #include "pmpc_schur.hpp"
 #define MODEL pmpc::RobotOCP
 namespace pmpc {
-template <> bool try_launch_schur_grids<MODEL>(PMPC_SCHUR_ARGS) {
-    PMPC_SCHUR_TRY(6, 1)
-    PMPC_SCHUR_TRY(5, 2)
-    PMPC_SCHUR_TRY(5, 3)
+template <> bool plan_schur_grids<MODEL>(PMPC_SCHUR_ARGS) {
+    PMPC_SCHUR_PLAN(6, 1)
+    PMPC_SCHUR_PLAN(5, 2)
+    PMPC_SCHUR_PLAN(5, 3)
     return false;
 }
 }  // namespace pmpc

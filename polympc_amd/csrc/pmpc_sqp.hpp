@@ -77,33 +77,52 @@ constexpr int PMPC_SQP_IN_PROGRESS = 3;   // internal: the instance continues in
 constexpr int PMPC_SQP_REDO = 4;          // internal: a QP of a condensed kernel gave up at its conditioning gate (PMPC_FLAG_ILLCOND) — the launcher's redo launch solves the instance again in the full KKT form
 constexpr int PMPC_REDO_MODE = -0x7fffffff - 1;   // it_begin of that redo launch: only instances with status PMPC_SQP_REDO run, from their guesses
 
+// The variant word of the fused SQP kernels (sqp_kernel, sqp_kernel_rr, sqp_schur_kernel in pmpc_launch.hpp) and of SqpDevice: template arguments
+// <Model, NN, MM, V>, V an OR of the flags below.
 // NN, MM > 0: compile-time QP size -> register-resident QP: NN+MM <= 64 one KKT row per lane (pmpc_qp_reg.hpp, REG1), 65..112 two rows per
 // lane (pmpc_qp_reg2.hpp, REG2: the QP alone is specialised, the other phases run the size-generic code with compile-time trip counts);
 // 0 -> LDS-resident QP
-// PROF: accumulate per-phase shader-clock cycles (separate kernel instantiation; costs 16+ VGPRs, off by default)
-// HU: Hessian-update policy compiled into a register-resident specialisation (0 dense damped BFGS, 1 block BFGS); the LDS-resident
-// kernels (NN == 0) select it at run time from settings.hessian_update
-// BIG: large-instance mode — the KKT factor is the tiled HBM workspace of pmpc_qp_big.hpp
-// POL: register-resident specialisation that carries the policy hooks the reference's tests install beside the default ones — the Ruiz
+// SQP_PROF (PROF): accumulate per-phase shader-clock cycles (separate kernel instantiation; costs 16+ VGPRs, off by default)
+// SQP_BLOCK_BFGS (HU = 1): Hessian-update policy compiled into a register-resident specialisation (without: dense damped BFGS, with: block BFGS); the
+//      LDS-resident kernels (NN == 0) select it at run time from settings.hessian_update
+// SQP_HBM (BIG, KHBM in the kernel): large-instance mode — the KKT factor is the tiled HBM workspace of pmpc_qp_big.hpp
+// SQP_TWO_WAVES (W2): the HBM-factor kernel compiled for two wavefronts per SIMD (256 registers)
+// SQP_HOOKS (POL): register-resident specialisation that carries the policy hooks the reference's tests install beside the default ones — the Ruiz
 //      preconditioner (qp_preconditioners.hpp:114-220) and the filter line search (line_search.hpp:31-98); the LDS / HBM-resident kernels (NN == 0)
 //      always carry them. A separate instantiation: the default register kernels stay free of the (cold) calls and their spills.
+// SQP_COND (CND): the CONDENSED register specialisation (pmpc_qp_cond.hpp) of a two-rows-per-lane kernel — everything as REG2 except the QP.
+// SQP_TEAM4 (WG4): the HBM-factor kernel on a workgroup of FOUR wavefronts per instance (BigTeam, pmpc_qp_big.hpp: small batches / lone instances);
+//      with SQP_TWO_WAVES the team kernel built for 256 registers — two workgroups per CU, its register budget from the launch bound alone
+enum : unsigned { SQP_PROF = 1, SQP_BLOCK_BFGS = 2, SQP_HBM = 4, SQP_TWO_WAVES = 8, SQP_HOOKS = 16, SQP_COND = 32, SQP_TEAM4 = 64 };
+// what every instantiation site of the launcher keeps to, checked at the kernel heads
+template <int NN, unsigned V> constexpr bool sqp_variant_ok() {
+    return (!(V & SQP_HBM) || NN == 0) &&                              // the HBM-factor kernels are size-generic
+           (!(V & SQP_TWO_WAVES) || (V & SQP_HBM)) &&                  // two waves per SIMD and the team of four: builds of the HBM-factor kernel
+           (!(V & SQP_TEAM4) || (V & SQP_HBM)) &&
+           (!(V & SQP_COND) || NN > 0) &&                              // condensed QP, hook builds, compiled-in block BFGS: register-resident kernels
+           (!(V & SQP_HOOKS) || NN > 0) &&                             // (size-generic kernels always carry the hooks)
+           (!(V & SQP_BLOCK_BFGS) || NN > 0) &&
+           V < 2 * SQP_TEAM4;                                          // no unknown bits
+}
 // PS: P * 256 + S of a BLOCK-STRUCTURED specialisation (pmpc_qp_schur.hpp; 0 = none): the Hessian is block diagonal per node (block BFGS or exact
 //      Hessians, NG = 0; NP = 1: the arrow shape, `hbrd` holds the border row with the corner and the border column) and lives as per-node blocks in LDS (`hblk`), J as its per-node blocks (`ocp.jblk`) + the differentiation matrix: the
 //      HBM workspace is not touched at all, and the QP is solved through the m x m Schur complement. NN, MM are the compile-time sizes there too.
-//      PS = -1: the CONDENSED register specialisation (pmpc_qp_cond.hpp) of a two-rows-per-lane kernel — everything as REG2 except the QP.
-template <class Model, int NN = 0, int MM = 0, bool PROF = false, int HU = 0, bool BIG = false, bool POL = false, int PS = 0>
+template <class Model, int NN = 0, int MM = 0, unsigned VARIANT = 0, int PS = 0>   // (VARIANT: the body has a V of its own)
 struct SqpDevice {
+    static_assert(sqp_variant_ok<NN, VARIANT>() && PS >= 0, "SqpDevice: variant flags that no kernel is built with");
+    static constexpr bool PROF = (VARIANT & SQP_PROF) != 0, BIG = (VARIANT & SQP_HBM) != 0, POL = (VARIANT & SQP_HOOKS) != 0;
+    static constexpr int HU = (VARIANT & SQP_BLOCK_BFGS) ? 1 : 0;
     static constexpr bool SCH = PS > 0;
-    static constexpr bool SLIM = PS == -2;   // large-instance mode compiled for two wavefronts per SIMD (256 registers)
-    static constexpr int BIG_NW = (PS == -3) ? 4 : 1;   // large-instance mode on a workgroup of four wavefronts (BigTeam, pmpc_qp_big.hpp): this object lives on the first one
+    static constexpr bool SLIM = BIG && (VARIANT & SQP_TWO_WAVES) && !(VARIANT & SQP_TEAM4);   // large-instance mode compiled for two wavefronts per SIMD (256 registers; not the team kernel)
+    static constexpr int BIG_NW = (BIG && (VARIANT & SQP_TEAM4)) ? 4 : 1;   // large-instance mode on a workgroup of four wavefronts (BigTeam, pmpc_qp_big.hpp): this object lives on the first one
     void* big_mail = nullptr;                           // the team's mailbox (LDS)
-    static constexpr bool CND = PS == -1;   // condensed register QP (pmpc_qp_cond.hpp): a two-rows-per-lane kernel (REG2) whose QP inverts S = H + sigma I + rho_box + A' diag(rho) A only
+    static constexpr bool CND = (VARIANT & SQP_COND) != 0;   // condensed register QP (pmpc_qp_cond.hpp): a two-rows-per-lane kernel (REG2) whose QP inverts S = H + sigma I + rho_box + A' diag(rho) A only
     static constexpr int SCH_P = PS / 256, SCH_S = PS % 256;
     static constexpr bool HOOKS = (NN == 0) || POL;
     using Dm = OcpDims<Model>;
     // Ruiz scaling is compiled into the kernels that carry the hooks (HOOKS: the LDS / HBM-resident kernels and the hook builds, POL, of the register kernels): in the default
     // register-resident kernels its three (cold, out-of-line) calls cost private-memory frames and call-ABI spills on the hot path.
-    // History of the condensed kernels (PS = -1): until late round 6 the launcher never routed preconditioner = 1 to them (Ruiz rescales the workspace the per-node blocks of A mirror),
+    // History of the condensed kernels (SQP_COND): until late round 6 the launcher never routed preconditioner = 1 to them (Ruiz rescales the workspace the per-node blocks of A mirror),
     // the calls were dead code there — and in round 4 / 5 they were what MISCOMPILED the hook build of the small condensed kernel (robot 11 nodes, 55 + 33, one row per lane: with the three
     // never-executed calls compiled in, the QP step of the primal-only lanes was lost — a VGPR -> AGPR copy of the lane id placed inside a partial-EXEC block, DESIGN.md hazard 3 /
     // EXPERIMENTS.md round 6), so round 5 compiled them out.

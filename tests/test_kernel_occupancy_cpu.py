@@ -5,31 +5,19 @@ one-wave kernels' budget)."""
 import os
 import re
 import subprocess
+import sys
 import tempfile
 
 import pytest
 
 import polympc_amd as pa
 
-LLVM = "/opt/rocm/lib/llvm/bin"
-MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from kernel_names import LLVM, SQP_COND, SQP_HBM, SQP_TWO_WAVES, code_objects, demangle, parse_sqp_kernel   # noqa: E402
 
 
 def _code_objects(tmp):
-    fat = os.path.join(tmp, "fat.bin")
-    subprocess.check_call(["objcopy", "-O", "binary", "--only-section=.hip_fatbin", pa.LIB_PATH, fat])
-    data = open(fat, "rb").read()
-    starts = [m.start() for m in re.finditer(re.escape(MAGIC), data)]
-    out = []
-    for n, (a, b) in enumerate(zip(starts, starts[1:] + [len(data)])):
-        bundle = os.path.join(tmp, f"b{n}.bin"); open(bundle, "wb").write(data[a:b])
-        targets = subprocess.run([f"{LLVM}/clang-offload-bundler", "--list", "--type=o", f"--input={bundle}"], capture_output=True, text=True).stdout.split()
-        for t in targets:
-            if "gfx950" in t:
-                co = os.path.join(tmp, f"b{n}.co")
-                subprocess.check_call([f"{LLVM}/clang-offload-bundler", "--unbundle", "--type=o", f"--input={bundle}", f"--targets={t}", f"--output={co}"])
-                out.append(co)
-    return out
+    return code_objects(pa.LIB_PATH, tmp)
 
 
 def _kernels(co):
@@ -44,32 +32,31 @@ def _kernels(co):
 @pytest.mark.skipif(not (os.path.exists(f"{LLVM}/clang-offload-bundler") and os.path.exists(f"{LLVM}/llvm-readelf")), reason="ROCm binutils not installed")
 def test_two_wave_kernels_fit_half_the_register_file():
     assert os.path.exists(pa.LIB_PATH)
-    pat = re.compile(r"sqp_kernel<pmpc::(\w+), (\d+), (\d+), (true|false), (\d+), (true|false), (true|false), (true|false), (true|false), (true|false)>")
     seen = {"reg1": 0, "big2": 0, "big1": 0, "reg2": 0}
     with tempfile.TemporaryDirectory() as tmp:
         objs = _code_objects(tmp)
         assert objs, "no gfx950 code object in the library"
         for co in objs:
             ks = list(_kernels(co))
-            names = subprocess.run(["c++filt"], input="\n".join(k[0] for k in ks), capture_output=True, text=True).stdout.splitlines()
-            for (mangled, vgpr, agpr), dn in zip(ks, names):
-                m = pat.search(dn)
-                if not m:
+            for (mangled, vgpr, agpr), dn in zip(ks, demangle(k[0] for k in ks)):
+                k = parse_sqp_kernel(dn)
+                if not k:
                     continue
-                nn, mm, khbm, w2 = int(m.group(2)), int(m.group(3)), m.group(6) == "true", m.group(7) == "true"
+                model, nn, mm, flags = k
                 # (.vgpr_count is the unified count: architected registers + accumulation file)
                 if nn > 0 and nn + mm <= 64:      # one KKT row per lane: PMPC_SQP_WAVES = 2
                     seen["reg1"] += 1
                     assert vgpr <= 256, f"{dn[:120]}: {vgpr} registers, two wavefronts per SIMD need <= 256"
-                elif khbm and w2:                 # HBM-factor kernel, two wavefronts per SIMD
+                elif flags & SQP_HBM and flags & SQP_TWO_WAVES:   # HBM-factor kernel, two wavefronts per SIMD
                     seen["big2"] += 1
                     assert vgpr <= 256, f"{dn[:120]}: {vgpr} registers, two wavefronts per SIMD need <= 256"
-                elif khbm:
+                elif flags & SQP_HBM:
                     seen["big1"] += 1
                     assert vgpr <= 512
                 elif nn > 0:
                     seen["reg2"] += 1
                     assert vgpr <= 512
+    print("two-wave register budgets: kernels per class", seen)
     assert seen["reg1"] > 0 and seen["big2"] > 0 and seen["big1"] > 0 and seen["reg2"] > 0, seen
 
 
@@ -102,6 +89,7 @@ def test_block_structured_kernels_do_not_spill_inside_the_swept_inverse():
                     if "scratch_store" in l or ("scratch_" in l and narrowed): bad.append(l.strip())
                 assert not bad, f"{head}: {len(bad)} scratch instructions under a narrowed EXEC / spill stores inside the swept inverse: {bad[:3]}"
                 checked += 1
+    print("block-structured kernels checked:", checked)
     assert checked >= 4
 
 
@@ -109,36 +97,41 @@ def test_block_structured_kernels_do_not_spill_inside_the_swept_inverse():
 def test_headline_kernel_has_no_scratch_and_condensed_kernels_none_in_the_admm_loop():
     """Two properties of the built code that cost a measurable share of a benchmark line when they break (compiler hazards 4 and 11): the
     headline kernel sqp_kernel<RobotOCP, 35, 21> has NO scratch traffic at all (round 4: the register-row BFGS spilled the head of the row of B behind its
-    loads — 1.18 instead of 1.13 ms per 4096), and the condensed register kernels (CND = true: config B, the 16-node robot grid) have none between the first
+    loads — 1.18 instead of 1.13 ms per 4096), and the condensed register kernels (flags == SQP_COND: config B, the 16-node robot grid) have none between the first
     and the last DPP mat-vec instruction, i.e. inside the ADMM loop."""
     headline = cond = 0
     with tempfile.TemporaryDirectory() as tmp:
         for co in _code_objects(tmp):
-            syms = subprocess.run([f"{LLVM}/llvm-readelf", "--notes", co], capture_output=True, text=True).stdout
-            if "sqp_kernelINS_8RobotOCPELi35ELi21ELb0ELi0ELb0ELb0ELb0ELb0E" not in syms and not re.search(r"sqp_kernelINS_\d+\w+?ELi\d+ELi\d+ELb0ELi0ELb0ELb0ELb0ELb1E", syms):
+            kinds = {}   # mangled name -> "headline" / "cond"
+            ks = [k[0] for k in _kernels(co)]
+            for mangled, dn in zip(ks, demangle(ks)):
+                k = parse_sqp_kernel(dn)
+                if k == ("RobotOCP", 35, 21, 0): kinds[mangled] = "headline"
+                elif k and k[3] == SQP_COND: kinds[mangled] = "cond"
+            if not kinds:
                 continue   # (disassembling every code object of the library takes half a minute)
             dis = subprocess.run([f"{LLVM}/llvm-objdump", "-d", "--no-show-raw-insn", co], capture_output=True, text=True).stdout
             for blk in re.split(r"\n(?=[0-9a-f]+ <)", dis):
                 head = blk.split("\n", 1)[0]
-                if "sqp_kernelINS_8RobotOCPELi35ELi21ELb0ELi0ELb0ELb0ELb0ELb0E" in head:
+                kind = kinds.get(head.split("<", 1)[1].rsplit(">", 1)[0]) if "<" in head else None
+                if kind == "headline":
                     n = sum("scratch_" in l for l in blk.split("\n"))
                     assert n == 0, f"{head}: {n} scratch instructions in the headline kernel"
                     headline += 1
-                elif re.search(r"sqp_kernelINS_\d+\w+?ELi\d+ELi\d+ELb0ELi0ELb0ELb0ELb0ELb1E", head):
+                elif kind == "cond":
                     lines = blk.split("\n")
                     dpp = [i for i, l in enumerate(lines) if "row_newbcast" in l]
                     assert dpp, head
                     inside = [l for l in lines[dpp[0]:dpp[-1]] if "scratch_" in l]
                     assert not inside, f"{head}: {len(inside)} scratch instructions inside the ADMM loop"
                     cond += 1
+    print("headline kernels:", headline, "condensed kernels:", cond)
     assert headline == 1 and cond >= 2, (headline, cond)
 
 
 def _exec_windows_of(co):
     """(kernels with an EXEC-window helper, helper bodies, [unproven bodies], [provable AGPR lane-validity violations]) of one code object — module-level so
     that a process pool can run it"""
-    import sys
-    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
     import tools_exec_regions as ter
     dis = subprocess.run([f"{LLVM}/llvm-objdump", "-d", "--no-show-raw-insn", "--symbolize-operands", co], capture_output=True, text=True).stdout
     kernels = bodies = 0
@@ -173,6 +166,7 @@ def test_exec_window_helpers_start_with_every_lane_enabled_and_no_spill_loses_la
         with ProcessPoolExecutor(max_workers=min(6, os.cpu_count() or 1)) as ex:
             res = list(ex.map(_exec_windows_of, objs))
     kernels = sum(r[0] for r in res); bodies = sum(r[1] for r in res)
+    print("data-flow analysis: kernels with EXEC-window helpers", kernels, "helper bodies", bodies, "code objects", len(res))
     bad = [b for r in res for b in r[2]]
     bad_agpr = [b for r in res for b in r[3]]
     assert kernels >= 100 and bodies >= 5000, (kernels, bodies)     # every register-resident QP kernel carries them (35 + 21: 32 bodies per inverse site)

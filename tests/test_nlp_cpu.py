@@ -3,7 +3,6 @@ include/polympc/register_nlp.hpp (tests/cpp/user_nlp.hip) with its built code ch
 the reference's NLP / SQP surface (tests/cpp/nlp_mirror_test.cpp) compiled by g++."""
 import ctypes as C
 import os
-import re
 import subprocess
 import sys
 import tempfile
@@ -15,8 +14,8 @@ CPP = os.path.join(HERE, "cpp")
 USER_SO = os.path.join(CPP, "libuser_nlp.so")
 SHAPES_SO = os.path.join(CPP, "libuser_nlp_shapes.so")
 MIRROR = os.path.join(CPP, "nlp_mirror_test")
-LLVM = "/opt/rocm/lib/llvm/bin"
-MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
+sys.path.insert(0, HERE)
+from kernel_names import LLVM, code_objects   # noqa: E402
 
 
 @pytest.fixture(scope="module")
@@ -53,23 +52,6 @@ def test_user_nlp_compiles_through_register_nlp(built):
     assert dims["Wide65"] == dict(nx=60, ne=5, ni=0, np=0, m=5)
 
 
-def _code_objects(path, tmp):
-    fat = os.path.join(tmp, "fat.bin")
-    subprocess.check_call(["objcopy", "-O", "binary", "--only-section=.hip_fatbin", path, fat])
-    data = open(fat, "rb").read()
-    starts = [m.start() for m in re.finditer(re.escape(MAGIC), data)]
-    out = []
-    for n, (a, b) in enumerate(zip(starts, starts[1:] + [len(data)])):
-        bundle = os.path.join(tmp, f"b{n}.bin"); open(bundle, "wb").write(data[a:b])
-        targets = subprocess.run([f"{LLVM}/clang-offload-bundler", "--list", "--type=o", f"--input={bundle}"], capture_output=True, text=True).stdout.split()
-        for t in targets:
-            if "gfx950" in t:
-                co = os.path.join(tmp, f"b{n}.co")
-                subprocess.check_call([f"{LLVM}/clang-offload-bundler", "--unbundle", "--type=o", f"--input={bundle}", f"--targets={t}", f"--output={co}"])
-                out.append(co)
-    return out
-
-
 def test_shapes_library_dims_match_checker(built):
     """the size-range problems of oracle/nlp_shapes.hpp, as registered on the device (tests/cpp/user_nlp_shapes.hip), have the dimensions
     of the checker's table"""
@@ -89,10 +71,9 @@ def test_user_nlp_library_has_no_unproven_exec_window_and_no_lane_losing_spill(b
     """The checks tests/test_kernel_occupancy_cpu.py makes of the product library, made of a USER-compiled library: the register QP's one-lane
     EXEC windows (pivot_lane_setup) start at full EXEC in every kernel the user's hipcc built, and no accumulation-register or scratch spill is
     read back with lanes its write did not cover. libuser_nlp_shapes.so holds the problems of 9 to 64 variables (up to 64 KKT rows)."""
-    sys.path.insert(0, HERE)
     import tools_exec_regions as ter
     with tempfile.TemporaryDirectory() as tmp:
-        objs = _code_objects(os.path.join(CPP, lib_name), tmp)
+        objs = code_objects(os.path.join(CPP, lib_name), tmp)
         assert objs
         kernels, bodies, bad, bad_agpr = 0, 0, [], []
         for co in objs:

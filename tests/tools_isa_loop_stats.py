@@ -1,5 +1,5 @@
 """Developer tool: instruction classes of the ADMM loop of a one-row-per-lane kernel, from a hipcc -save-temps ISA listing (*.s).
-   python tests/tools_isa_loop_stats.py pmpc_model_robot-hip-amdgcn-amd-amdhsa-gfx950.s "sqp_kernel<pmpc::RobotOCP, 35, 21, false, 0, false"
+   python tests/tools_isa_loop_stats.py pmpc_model_robot-hip-amdgcn-amd-amdhsa-gfx950.s "sqp_kernel<pmpc::RobotOCP, 35, 21, 0u>"   (the last argument: the variant flags SQP_* of pmpc_sqp.hpp)
 The loop is found by what only it contains: the DPP mat-vec of RegKkt::apply (v_fmac_f64_dpp). It is the innermost loop around those instructions — from
 the last label in front of the first of them that a later backward branch names, to that branch — and holds the ADMM iteration and the residual
 evaluation (a sibling of tests/tools_isa_stats.py, which counts whole kernels)."""

@@ -21,13 +21,15 @@ for name in ["sq1", "sq2", "fetch", "write", "tcc", "calfetch", "calwrite"]:
 # HBM traffic per launch of the bench kernel, corrected with the calibration run (MI355X_MICROARCH.md, HBM / rocprofv3
 # section): the counters are in KiB-sized units; the calibration kernel reads 2^30 B and writes 2^29 B with the same
 # 8-byte-per-lane access width, which gives the byte value of one counter unit for this access pattern.
-import re
-BENCH_KERNEL = re.compile(r"RobotOCP, 35, 21, false, 0(, false)+>")   # the default-policy specialisation of the bench kernel (every template flag after HU = 0 off)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from kernel_names import parse_sqp_kernel
+def BENCH_KERNEL(name):   # the default-policy specialisation of the bench kernel (no variant flag set; the positional names of older profiles decode to the same)
+    return parse_sqp_kernel(name) == ("RobotOCP", 35, 21, 0)
 def _one(d, key):
-    # the bench kernel is the default-policy specialisation (template arguments ..., PROF = false, HU = 0, KHBM = false); bench.py also
-    # launches the block-BFGS specialisation (HU = 1) for its variant leg, which is reported but not used for the traffic figure
+    # the bench kernel is the default-policy specialisation (variant flags 0); bench.py also
+    # launches the block-BFGS specialisation (SQP_BLOCK_BFGS) for its variant leg, which is reported but not used for the traffic figure
     ks = [k for k in d if k.startswith(key)]
-    pref = [k for k in ks if "stream_rw" in k or BENCH_KERNEL.search(k)]
+    pref = [k for k in ks if "stream_rw" in k or BENCH_KERNEL(k)]
     if not pref:   # not the bench command: the kernel that moves the most data
         pref = sorted(ks, key=lambda k: -d[k]["per_launch_mean"] * d[k]["launches"])
     return d[pref[0]]["per_launch_mean"] if pref else None
@@ -38,7 +40,7 @@ try:
     write = _one(out["write"], "WRITE_SIZE") * w_unit
     out["traffic"] = {"fetch_bytes_per_launch": fetch, "write_bytes_per_launch": write, "bytes_per_launch": fetch + write,
                       "bytes_per_counter_unit": {"FETCH_SIZE": f_unit, "WRITE_SIZE": w_unit},
-                      "kernel": [k for k in sorted(out["fetch"], key=lambda k: -out["fetch"][k]["per_launch_mean"] * out["fetch"][k]["launches"])][0] if not any(BENCH_KERNEL.search(k) for k in out["fetch"]) else "sqp_kernel<RobotOCP,35,21> (bench.py --steps 5 --warmup 1, config A, batch 4096)"}
+                      "kernel": [k for k in sorted(out["fetch"], key=lambda k: -out["fetch"][k]["per_launch_mean"] * out["fetch"][k]["launches"])][0] if not any(BENCH_KERNEL(k) for k in out["fetch"]) else "sqp_kernel<RobotOCP,35,21> (bench.py --steps 5 --warmup 1, config A, batch 4096)"}
 except Exception as e:  # incomplete collection
     out["traffic"] = None
 try:   # L2 hit rate of the kernel the traffic figure is about
