@@ -104,8 +104,14 @@ __global__ __launch_bounds__((V & SQP_TEAM4) ? 256 : 64, ((NN > 0 && NN + MM <= 
     // it_begin < 0: resume mode (the launch behind the round-robin kernel, sqp_kernel_rr below): every instance continues from the iteration its own record holds
     if (it_begin < 0) it_begin = __builtin_amdgcn_readfirstlane(info[b].iter);
     const int P = cd->P, S = cd->S;
-    Ocp<Model> ocp(model, P, S, cd->t_scale);
+    // register-resident instantiations (NN > 0): the node count, and with it n, m, mi and the LDS carve below, are constants of this body (PMPC_STATIC_LAYOUT, pmpc_ocp.hpp).
+    // Valid because plan_reg launches <NN, MM> only where a.P * a.S + 1 == NNODES; P and S themselves stay run-time values
+    constexpr int KN = static_nodes<Model, NN, MM>();
+    constexpr bool ROLLED = KN > 0;   // the cold loops below keep a run-time bound (rolled_bound)
+    Ocp<Model, KN> ocp(model, P, S, cd->t_scale);
     const int n = ocp.dm.n, m = ocp.dm.m, mi = ocp.dm.mi;
+    if constexpr (KN > 0) static_assert(decltype(ocp)::Dm::n == NN && decltype(ocp)::Dm::m == MM, "sqp_kernel: <NN, MM> is not a grid of this model");
+    double* const lds = lds_origin<decltype(ocp.s)::TAIL_DW>(smem);   // static layout: the carve is a table of constant offsets from byte 0 of LDS (lds_origin, pmpc_qp.hpp); else smem
     QpLds qw; SqpLds v;
     // KHBM, large-instance mode: the KKT factor lives in an HBM workspace, and so does everything else except the vectors the substitutions
     // hammer (the QP solution x / y and the right-hand side): the SQP vectors (20 of length n or n+m), the per-node AD staging and the remaining
@@ -129,7 +135,7 @@ __global__ __launch_bounds__((V & SQP_TEAM4) ? 256 : 64, ((NN > 0 && NN + MM <= 
         hq += QpLds::doubles_rest(n, m);
         ocp.jblk = hq; ocp.gblk = ocp.jblk + (size_t)ocp.dm.NN * Model::NX * OcpDims<Model>::JBS; ocp.keep_blk = true;   // block-sparse copy of J for the condensed linear algebra (pmpc_qp_big.hpp)
     } else {
-        p = (NN > 0) ? qw.carve_xy(smem, n, m) : qw.carve(smem, n, ss.qp_solver == 1 ? m + n : m);   // ADMM: stacked constraint rows
+        p = (NN > 0) ? qw.carve_xy(lds, n, m) : qw.carve(smem, n, ss.qp_solver == 1 ? m + n : m);   // ADMM: stacked constraint rows
         p = v.carve(p, n, m, mi);
         stage0 = p;
         p = ocp.s.carve(p, P, S);
@@ -140,6 +146,12 @@ __global__ __launch_bounds__((V & SQP_TEAM4) ? 256 : 64, ((NN > 0 && NN + MM <= 
         if constexpr (CND && POL) {   // its hook builds with the Ruiz preconditioner on: room for the tables per state index (the launcher sized the allocation by the same rule)
             if (ss.preconditioner == 1) QP_STAGING = cond_qp_staging_ws<NN, MM, NN / (Model::NX + Model::NU), Model::NX>();
         }
+        if constexpr (decltype(ocp.s)::TAIL_DW) {   // static layout: [node constants | staging, at least the QP's] here, D / w behind the parameters and the filter below — the same doubles in another order
+            static_assert(SqpLds::carved(NN, MM, Model::NG * KN) + 2 * NN + 8 == SqpLds::doubles(NN, MM, Model::NG * KN), "SqpLds::carve ends where SqpLds::doubles says (which has always counted 2 n + 8 spare doubles)");
+            constexpr size_t NC = decltype(ocp.s)::node_const_doubles(KN), NS = decltype(ocp.s)::node_staging_doubles(KN);
+            static_assert(NC + NS + decltype(ocp.s)::dw_doubles(1) + 8 == OcpLds<Model>::doubles(1, KN - 1) && decltype(ocp.s)::dw_doubles(1) + NC == OcpLds<Model>::const_doubles(1, KN - 1), "the constant layout ends where OcpLds::doubles says");
+            if ((size_t)(p - stage0) < (size_t)QP_STAGING + 2 + NC) p = stage0 + QP_STAGING + 2 + NC;
+        } else
         if (NN > 0 && (size_t)(p - stage0) < (size_t)QP_STAGING + 2 + ocp.s.const_doubles(P, S)) p = stage0 + QP_STAGING + 2 + ocp.s.const_doubles(P, S);
         stage_end = p;   // end of the per-node staging block: what follows (static parameters, filter) stays live during the line search
     }
@@ -151,6 +163,7 @@ __global__ __launch_bounds__((V & SQP_TEAM4) ? 256 : 64, ((NN > 0 && NN + MM <= 
     ocp.d = dL;
     double* filt = nullptr;   // LSFilter of this instance (line_search = 1; the register-resident specialisations do not carry it)
     if constexpr (NN == 0 || POL) { filt = p; p += FILTER_LDS_DOUBLES; }
+    if constexpr (decltype(ocp.s)::TAIL_DW) p = ocp.s.carve_dw(p, P);   // the two arrays sized by P: nothing but the Jacobi workspace lies behind them
     if constexpr (WG4) {
         // wavefronts 1 .. 3 of a four-wavefront team (BigTeam): every pointer above is set up on them as on the first wavefront — the carve is pure
         // arithmetic —, no data has moved yet; from here on they run the routines the first wavefront posts (big_helper_loop) and nothing else
@@ -180,16 +193,17 @@ __global__ __launch_bounds__((V & SQP_TEAM4) ? 256 : 64, ((NN > 0 && NN + MM <= 
     // kernels 4 .. 10 % through register pressure alone (EXPERIMENTS.md round 5).
     constexpr bool BOUNDS_RULE = NN > 0 && (CND || NN + MM <= WAVE);
     bool loose = false;
-    for (int i = ln; i < n; i += WAVE) {
+    const int n_rt = rolled_bound<ROLLED>(n), nm_rt = rolled_bound<ROLLED>(m + n), mi_rt = rolled_bound<ROLLED>(mi);
+    for (int i = ln; i < n_rt; i += WAVE) {
         v.x[i] = (it_begin > 0) ? x[(size_t)b * n + i] : (x_guess ? x_guess[(size_t)b * n + i] : 0.0);
         const double lbi = lbx[(size_t)b * n + i], ubi = ubx[(size_t)b * n + i];
         v.lbx[i] = lbi; v.ubx[i] = ubi;
         if constexpr (BOUNDS_RULE) loose |= (i >= ocp.dm.VARX) && (lbi < -LOOSE_BOUNDS_THRESH) && (ubi > LOOSE_BOUNDS_THRESH);   // classify_bounds(...) == 2 on a control / parameter
         if (it_begin > 0) { v.lg[i] = sst[i]; v.step[i] = sst[n + i]; }
     }
-    for (int i = ln; i < m + n; i += WAVE)
+    for (int i = ln; i < nm_rt; i += WAVE)
         v.lam[i] = (it_begin > 0) ? lam[(size_t)b * (m + n) + i] : (lam_guess ? lam_guess[(size_t)b * (m + n) + i] : 0.0);
-    for (int i = ln; i < mi; i += WAVE) {
+    for (int i = ln; i < mi_rt; i += WAVE) {
         v.lbg[i] = lbg ? lbg[(size_t)b * mi + i] : -INFINITY;
         v.ubg[i] = ubg ? ubg[(size_t)b * mi + i] : INFINITY;
     }
@@ -212,7 +226,7 @@ __global__ __launch_bounds__((V & SQP_TEAM4) ? 256 : 64, ((NN > 0 && NN + MM <= 
     sqp.eig = eigw;
     sqp.trace = ss.iteration_trace ? ss.iteration_trace + (size_t)b * (size_t)ss.iteration_trace_capacity * PMPC_TRACE_DOUBLES : nullptr;
     sqp.tr = ocp.s.fval;   // first per-node staging array: everything from here on is dead while the QP runs
-    if constexpr (NN + MM > 112) sqp.tr += (ocp.s.fval - smem) & 1;   // (on a 16-byte boundary there: the 8 x 8 register path reads its LDS tiles in 16-byte units. Only there — a second, separately live pointer cost the 7-node kernel a spill inside its ADMM loop)
+    if constexpr (NN + MM > 112) sqp.tr += (ocp.s.fval - lds) & 1;   // (on a 16-byte boundary there: the 8 x 8 register path reads its LDS tiles in 16-byte units. Only there — a second, separately live pointer cost the 7-node kernel a spill inside its ADMM loop)
     {   // side-by-side line search: G candidates x (m constraint values + NN Lagrange values) + 3 scalars each, in the same region
         const int G = WAVE / ocp.dm.NN;
         const size_t need = (size_t)G * (m + ocp.dm.NN + 3);
@@ -225,9 +239,10 @@ __global__ __launch_bounds__((V & SQP_TEAM4) ? 256 : 64, ((NN > 0 && NN + MM <= 
     sqp.qp_flags = flags0;
     if (it_begin > 0) { const pmpc_sqp_info prev = info[b]; sqp.qp_iter_total = prev.qp_solver_iter; sqp.qp_flags = prev.flags; sqp.cost_log = prev.cost; }
     sqp.solve(si, it_begin, it_end);
-    if (si.status == PMPC_SQP_IN_PROGRESS && sst) for (int i = ln; i < n; i += WAVE) { sst[i] = v.lg[i]; sst[n + i] = v.step[i]; }
-    for (int i = ln; i < n; i += WAVE) x[(size_t)b * n + i] = v.x[i];
-    for (int i = ln; i < m + n; i += WAVE) lam[(size_t)b * (m + n) + i] = v.lam[i];
+    const int n_out = rolled_bound<ROLLED>(n), nm_out = rolled_bound<ROLLED>(m + n);
+    if (si.status == PMPC_SQP_IN_PROGRESS && sst) for (int i = ln; i < n_out; i += WAVE) { sst[i] = v.lg[i]; sst[n + i] = v.step[i]; }
+    for (int i = ln; i < n_out; i += WAVE) x[(size_t)b * n + i] = v.x[i];
+    for (int i = ln; i < nm_out; i += WAVE) lam[(size_t)b * (m + n) + i] = v.lam[i];
     if (ln == 0) info[b] = si;
     if constexpr (NN == 0 || POL) {   // (an instance that gave up leaves the carried filter as it found it: the redo launch starts from the same filter)
         if (ss.line_search == 1 && ss.filter_state != nullptr && si.status != PMPC_SQP_REDO && ln < PMPC_FILTER_STATE_DOUBLES) ss.filter_state[(size_t)b * PMPC_FILTER_STATE_DOUBLES + ln] = filt[ln];
@@ -408,16 +423,19 @@ __global__ __launch_bounds__(64, PMPC_SQP_WAVES) void sqp_kernel_rr(Model model,
     static_assert(NN > 0 && NN + MM <= WAVE && (V & ~SQP_BLOCK_BFGS) == 0, "round-robin execution exists for the one-row-per-lane register path, default hooks");
     extern __shared__ double smem[];
     const int P = cd->P, S = cd->S;
-    Ocp<Model> ocp(model, P, S, cd->t_scale);
+    constexpr int KN = static_nodes<Model, NN, MM>();   // the carve of sqp_kernel<NN, MM> (see there): sizes and offsets are constants of this body
+    Ocp<Model, KN> ocp(model, P, S, cd->t_scale);
     const int n = ocp.dm.n, m = ocp.dm.m, mi = ocp.dm.mi;
     QpLds qw; SqpLds v;
-    double* p = qw.carve_xy(smem, n, m);
+    double* p = qw.carve_xy(lds_origin<decltype(ocp.s)::TAIL_DW>(smem), n, m);
     p = v.carve(p, n, m, mi);
     double* stage0 = p;
     p = ocp.s.carve(p, P, S);
-    if ((size_t)(p - stage0) < (size_t)reg_qp_staging<NN + MM>() + 2 + ocp.s.const_doubles(P, S)) p = stage0 + reg_qp_staging<NN + MM>() + 2 + ocp.s.const_doubles(P, S);
+    const size_t cst_ahead = decltype(ocp.s)::TAIL_DW ? decltype(ocp.s)::node_const_doubles(KN) : ocp.s.const_doubles(P, S);   // constants between stage0 and the staging
+    if ((size_t)(p - stage0) < (size_t)reg_qp_staging<NN + MM>() + 2 + cst_ahead) p = stage0 + reg_qp_staging<NN + MM>() + 2 + cst_ahead;
     const double* stage_end = p;
     double* dL = p; p += (Model::ND > 0 ? Model::ND : 1);
+    if constexpr (decltype(ocp.s)::TAIL_DW) p = ocp.s.carve_dw(p, P);
     ocp.d = dL;
     const int ln = lane_id();
     ocp.stage_constants(cd);

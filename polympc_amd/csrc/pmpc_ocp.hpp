@@ -31,6 +31,17 @@ struct ChebData {
     double tn[MAX_NODES];                 // time nodes, descending (node 0 = t_stop)
 };
 
+// STATIC LAYOUT of the register-resident kernels (NN > 0). Their instantiation fixes the node count K = MM / (NX + NG), and with it every size OcpDims derives
+// and every LDS offset of the carve — which the kernels used to compute from cd->P, cd->S at run time all the same (150 scalar multiplies at the kernel head, ~45
+// LDS pointers, most of the 252 scalar values the headline kernel kept in spill lanes: a readlane, its wait state and an add in front of most LDS accesses). Developer switch for the
+// A/B of its stages (profiles/r10_ab_static_layout.txt): 0 run-time sizes and pointers; 1 the sizes are constants of the kernel body (OcpDimsCT); 2 also the
+// addresses: D (with its extra row) and w — the only arrays whose size depends on P, not on the node count — move behind everything node-sized (OcpLds::carve_dw),
+// so that every other LDS array sits at a constant offset from byte 0 of LDS (lds_origin, pmpc_qp.hpp). P and S stay run-time values: 7 nodes are (6,1), (3,2), (2,3) or (1,6). What makes the
+// constants valid is the launcher's run-time check `a.P * a.S + 1 == NNODES` (plan_reg, pmpc_launch.hpp). The arithmetic is untouched: bit-identical results.
+#ifndef PMPC_STATIC_LAYOUT
+#define PMPC_STATIC_LAYOUT 2
+#endif
+
 template <class Model>
 struct OcpDims {
     enum { NX = Model::NX, NU = Model::NU, NP = Model::NP, ND = Model::ND, NG = Model::NG, NDER = NX + NU + NP,
@@ -45,10 +56,33 @@ struct OcpDims {
     }
 };
 
+// the same sizes for a node count KN known at compile time (register-resident kernels, PMPC_STATIC_LAYOUT >= 1): constants, read through the same names
+template <class Model, int KN>
+struct OcpDimsCT {
+    static_assert(KN > 0, "OcpDimsCT: a compile-time node count");
+    enum { NX = Model::NX, NU = Model::NU, NP = Model::NP, ND = Model::ND, NG = Model::NG, NDER = NX + NU + NP, JBS = OcpDims<Model>::JBS };
+    static constexpr int NN = KN, VARX = NX * KN, VARU = NU * KN, n = VARX + VARU + NP, me = VARX, mi = NG * KN, m = me + mi;
+    __host__ __device__ OcpDimsCT(int, int) {}   // (P, S: P * S + 1 == KN is the launcher's check)
+    __host__ __device__ static constexpr int gidx(int k, int i) {
+        return i < NX ? k * NX + i : (i < NX + NU ? VARX + k * NU + (i - NX) : VARX + VARU + (i - NX - NU));
+    }
+};
+template <class Model, int KN> struct OcpDimsSel { using type = OcpDimsCT<Model, KN>; };
+template <class Model> struct OcpDimsSel<Model, 0> { using type = OcpDims<Model>; };
+// node count an Ocp / OcpLds of a kernel with NN variables and MM constraint rows is built for (0: run-time sizes)
+template <class Model, int NN, int MM> constexpr int static_nodes() { return (PMPC_STATIC_LAYOUT >= 1 && NN > 0) ? MM / (Model::NX + Model::NG) : 0; }
+// a loop bound the compiler must treat as a run-time value: the cold loops of the kernel heads and tails (prologue loads, stage_constants, epilogue stores) stay
+// rolled — unrolled by a known trip count they issue their loads in bulk and cost the headline kernel its last ten registers (256 + scratch)
+template <bool OPAQUE> __device__ __forceinline__ int rolled_bound(int v) {
+    if constexpr (OPAQUE) asm volatile("" : "+s"(v));
+    return v;
+}
+
 // per-instance LDS staging for the transcription
-template <class Model>
+template <class Model, int KN = 0>
 struct OcpLds {
-    using Dm = OcpDims<Model>;
+    using Dm = typename OcpDimsSel<Model, KN>::type;
+    static constexpr bool TAIL_DW = KN > 0 && PMPC_STATIC_LAYOUT >= 2;   // D / w carved by carve_dw, behind everything node-sized
     enum { NX = Dm::NX, NU = Dm::NU, NP = Dm::NP, NG = Dm::NG, NDER = Dm::NDER };
     double *D, *w, *tn;                                 // collocation constants; D is followed by Dl[t] = -D(0, P - t), the last node's row of J (:845-846)
     double *nd, *nw1, *nw2; int* nsr;                   // per node: D self entry, the two quadrature weights * t_scale, packed (flags, segment, row)
@@ -56,19 +90,27 @@ struct OcpLds {
     double *Lhes, *dhes;                                // per node: d2L (NDER^2), sum lam * d2(f,g) (NDER^2)
     double *Mval, *Mgrad, *Mhes;                        // Mayer term at node 0
     double *DX;                                         // D*X per node (NX)
-    __host__ __device__ static size_t doubles(int P, int S) {
+    __host__ __device__ static constexpr size_t doubles(int P, int S) {
         const int NN = P * S + 1;
         return const_doubles(P, S) + (size_t)NN * (NX + NX * NDER + 1 + NDER + NG + NG * NDER + 2 * NDER * NDER + NX) +
                1 + NDER + NDER * NDER + 8;
     }
     // collocation constants come first; everything after them is per-linearisation staging
-    __host__ __device__ static size_t const_doubles(int P, int S) {
+    __host__ __device__ static constexpr size_t const_doubles(int P, int S) {
         const int NN = P * S + 1;
         return (size_t)(P + 1) * (P + 1) + (P + 1) /*Dl*/ + (P + 1) + NN + 3 * (size_t)NN + (size_t)(NN + 1) / 2;
     }
+    __host__ __device__ static constexpr size_t dw_doubles(int P) { return (size_t)(P + 1) * (P + 1) + (P + 1) /*Dl*/ + (P + 1); }
+    // the constants and the staging whose size the node count fixes (TAIL_DW: all of carve())
+    __host__ __device__ static constexpr size_t node_const_doubles(int NN) { return (size_t)NN + 3 * (size_t)NN + (size_t)(NN + 1) / 2; }
+    __host__ __device__ static constexpr size_t node_staging_doubles(int NN) {
+        return (size_t)NN * (NX + NX * NDER + 1 + NDER + NG + NG * NDER + 2 * NDER * NDER + NX) + 1 + NDER + NDER * NDER;
+    }
+    __device__ __forceinline__ double* carve_dw(double* p, int P) { D = p; p += (P + 1) * (P + 1) + (P + 1); w = p; p += P + 1; return p; }
     __device__ __forceinline__ double* carve(double* p, int P, int S) {
-        const int NN = P * S + 1;
-        D = p; p += (P + 1) * (P + 1) + (P + 1); w = p; p += P + 1; tn = p; p += NN;
+        const int NN = KN > 0 ? KN : P * S + 1;
+        if constexpr (!TAIL_DW) p = carve_dw(p, P);
+        tn = p; p += NN;
         nd = p; p += NN; nw1 = p; p += NN; nw2 = p; p += NN; nsr = (int*)p; p += (NN + 1) / 2;
         fval = p; p += NN * NX; fjac = p; p += NN * NX * NDER; Lval = p; p += NN; Lgrad = p; p += NN * NDER;
         gval = p; p += NN * NG; gjac = p; p += NN * NG * NDER; Lhes = p; p += NN * NDER * NDER; dhes = p; p += NN * NDER * NDER;
@@ -77,9 +119,10 @@ struct OcpLds {
     }
 };
 
-template <class Model>
+template <class Model, int KN = 0>   // KN > 0: node count fixed at compile time (OcpDimsCT)
 struct Ocp {
-    using Dm = OcpDims<Model>;
+    using Dm = typename OcpDimsSel<Model, KN>::type;
+    static constexpr bool STATIC = KN > 0;
     enum { NX = Dm::NX, NU = Dm::NU, NP = Dm::NP, ND = Dm::ND, NG = Dm::NG, NDER = Dm::NDER };
     using ad1 = Dual<double, NDER>;
     using ad2c = Dual<ad1, 1>;  // one outer seed direction at a time
@@ -88,7 +131,7 @@ struct Ocp {
     Dm dm;
     int P, S;
     double ts;
-    OcpLds<Model> s;
+    OcpLds<Model, KN> s;
     const double* d;  // static parameters of this instance (ND)
     // block-sparse copy of J for pmpc_jview.hpp (register-resident kernels): the per-node blocks assemble_first_order writes into J, kept in
     // an LDS region that outlives the per-node staging (which the QP's staging aliases); keep_blk says whether the two pointers are set
@@ -103,11 +146,12 @@ struct Ocp {
         for (int i = ln; i < (P + 1) * (P + 1); i += WAVE) s.D[i] = cd->D[i];
         for (int i = ln; i <= P; i += WAVE) s.D[(P + 1) * (P + 1) + i] = -cd->D[(P - i) * (P + 1)];
         for (int i = ln; i <= P; i += WAVE) s.w[i] = cd->w[i];
-        for (int i = ln; i < dm.NN; i += WAVE) s.tn[i] = cd->tn[i];
+        const int nn_rt = rolled_bound<STATIC>(dm.NN);   // (a cold loop: it stays rolled)
+        for (int i = ln; i < nn_rt; i += WAVE) s.tn[i] = cd->tn[i];
         // per-node table: everything the hot loops would otherwise derive from k / P and k % P (integer divisions by a run-time
         // value) — (segment, row) of seg_row, the node's own D entry, and the cost-gradient weights of :1218-1240 with the
         // conditions under which they apply (bit 30: node closes a segment, bit 29: node opens / lies inside one)
-        for (int k = ln; k < dm.NN; k += WAVE) {
+        for (int k = ln; k < nn_rt; k += WAVE) {
             int seg, row;
             if (k == dm.NN - 1) { seg = S - 1; row = P; } else { seg = k / P; row = k % P; }
             const bool closes = (k % P == 0) && k > 0, inside = k < dm.NN - 1;

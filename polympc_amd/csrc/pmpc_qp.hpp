@@ -37,6 +37,18 @@ __device__ __forceinline__ int lane_id() { int l = threadIdx.x & (WAVE - 1); asm
 __device__ __forceinline__ void wfence() { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); }
 __device__ __forceinline__ void wsync() { wfence(); __builtin_amdgcn_wave_barrier(); }
 
+// Origin of a kernel's dynamic LDS for a carve at constant offsets (PMPC_STATIC_LAYOUT >= 2, pmpc_ocp.hpp). The address of an `extern __shared__` array reaches
+// instruction selection as an opaque "static LDS size" node: every `smem + constant` becomes a scalar add of its own, hoisted to the kernel head and kept in — or
+// spilled from — an SGPR (118 of them in the headline kernel), and no constant reaches the offset field of a ds instruction. LITERAL = true: the origin as the
+// integer it is — byte 0 of LDS, these kernels declare no static __shared__ variable (tests/test_static_layout_cpu.py reads .group_segment_fixed_size = 0 of every
+// one of them from the built code) — so that `origin + constant + lane` selects to `ds_read v_lane offset:constant`. LDS address 0 is an ordinary address (the
+// null pointer of the local address space is -1), but the optimiser's null is the all-zero pointer of EVERY address space: a generic pointer cast from local
+// address 0 folds to the generic null and every access through it becomes a flat one. Hence one double below local address 8, which nothing folds.
+template <bool LITERAL> __device__ __forceinline__ double* lds_origin(double* smem) {
+    if constexpr (LITERAL) { typedef __attribute__((address_space(3))) double lds_double; return (double*)(lds_double*)(size_t)sizeof(double) - 1; }
+    else return smem;
+}
+
 // A zero the optimiser cannot see through. Added to the per-lane element offset of global-memory accesses inside the SQP /
 // ADMM loops, it keeps their address arithmetic next to the access: otherwise every one of the O(n) distinct 64-bit
 // addresses is computed once outside the loops (they are loop-invariant) and then lives in — or is spilled from — a

@@ -59,8 +59,12 @@ struct TriDeal {
 
 struct SqpLds {
     double *x, *lam, *lam_k, *h, *lg, *lgn, *al, *au, *lx, *ux, *lbx, *ubx, *lbg, *ubg, *step, *xs, *cb, *t1, *t2, *t3;
-    __host__ __device__ static size_t doubles(int n, int m, int mi) {
+    __host__ __device__ static constexpr size_t doubles(int n, int m, int mi) {
         return 12 * (size_t)n + 2 * (size_t)(m + n) + 3 * (size_t)m + 2 * (size_t)mi + 3 * (size_t)(n + m) + 8;
+    }
+    // what carve() advances by, array by array in its order (the static layout's check against doubles(): carve ends 2 n + 8 doubles short of it)
+    __host__ __device__ static constexpr size_t carved(int n, int m, int mi) {
+        return (size_t)n + (m + n) + (m + n) + n + n + n + m + m + n + n + n + n + mi + mi + n + n + m + (n + m) + (n + m) + (n + m);
     }
     __device__ __forceinline__ double* carve(double* p, int n, int m, int mi) {
         x = p; p += n; lam = p; p += m + n; lam_k = p; p += m + n; h = p; p += n; lg = p; p += n; lgn = p; p += n;
@@ -119,7 +123,9 @@ struct SqpDevice {
     static constexpr bool CND = (VARIANT & SQP_COND) != 0;   // condensed register QP (pmpc_qp_cond.hpp): a two-rows-per-lane kernel (REG2) whose QP inverts S = H + sigma I + rho_box + A' diag(rho) A only
     static constexpr int SCH_P = PS / 256, SCH_S = PS % 256;
     static constexpr bool HOOKS = (NN == 0) || POL;
-    using Dm = OcpDims<Model>;
+    static constexpr int OCP_KN = (PS > 0) ? 0 : static_nodes<Model, NN, MM>();   // node count the kernel's Ocp is built for (PMPC_STATIC_LAYOUT; the block-structured kernels pass P, S as constants anyway)
+    using OcpT = Ocp<Model, OCP_KN>;
+    using Dm = typename OcpT::Dm;
     // Ruiz scaling is compiled into the kernels that carry the hooks (HOOKS: the LDS / HBM-resident kernels and the hook builds, POL, of the register kernels): in the default
     // register-resident kernels its three (cold, out-of-line) calls cost private-memory frames and call-ABI spills on the hot path.
     // History of the condensed kernels (SQP_COND): until late round 6 the launcher never routed preconditioner = 1 to them (Ruiz rescales the workspace the per-node blocks of A mirror),
@@ -133,7 +139,7 @@ struct SqpDevice {
     static constexpr bool REG2 = !SCH && NN > 0 && NN + MM > WAVE;     // two KKT rows per lane
     double *hblk = nullptr, *hbrd = nullptr /* NP = 1: border row + corner, border column (pmpc_qp_schur.hpp) */, *qblk = nullptr, *xsc = nullptr, *dsc = nullptr, *dtab = nullptr;   // SCH: Hessian blocks, Q blocks, the exchange vectors and the D~ tables of the QP (LDS)
     static constexpr int MEMCH = BIG ? BIG_MEM_BATCH : 8;      // loads in flight per lane in the row walks over the BFGS matrix in HBM
-    Ocp<Model>& ocp;
+    OcpT& ocp;
     SqpLds& v;
     QpLds& qw;
     double* lsbuf = nullptr;   // LDS scratch of the side-by-side line search (aliases the MFMA staging, free outside the QP)
@@ -170,8 +176,9 @@ struct SqpDevice {
 #ifdef PMPC_EXPERIMENT_WG_STAMPS
     long long t_start_stamp = wall_clock64();
 #endif
-    __device__ SqpDevice(Ocp<Model>& o, SqpLds& v_, QpLds& q_, double* H_, double* A_, const pmpc_sqp_settings& s, const pmpc_qp_settings& q)
-        : ocp(o), v(v_), qw(q_), Hw(H_), Aw(A_), ldw(o.dm.n + o.dm.m), ss(s), qs(q), n(o.dm.n), m(o.dm.m), me(o.dm.me), mi(o.dm.mi) {}
+    __device__ SqpDevice(OcpT& o, SqpLds& v_, QpLds& q_, double* H_, double* A_, const pmpc_sqp_settings& s, const pmpc_qp_settings& q)
+        : ocp(o), v(v_), qw(q_), Hw(H_), Aw(A_), ldw(o.dm.n + o.dm.m), ss(s), qs(q), n(rolled_bound<(OCP_KN > 0)>(o.dm.n)), m(rolled_bound<(OCP_KN > 0)>(o.dm.m)),
+          me(rolled_bound<(OCP_KN > 0)>(o.dm.me)), mi(rolled_bound<(OCP_KN > 0)>(o.dm.mi)) {}   // (static layout: the four run-time members stay run-time values — they bound the cold loops (serial line search, the fallback of the rank-2 update), which stay rolled; the hot paths read n_ct() .. mi_ct(), and the stride ldw is a constant)
 
     // constraints_violation_impl :423-444 (sequential sums, reference association order)
     __device__ __forceinline__ double constraints_violation(const double* xx) {
