@@ -721,21 +721,61 @@ public:
     pmpc_status step(const double* x0, double* u0) noexcept {
         pmpc_context* ctx = context();
         if (!ctx) return last_error();
-        if (!m_batch) {
-            const pmpc_status st = device_binding<OCP>::mpc_create(ctx, problem, OCP::POLY_ORDER, OCP::NUM_SEGMENTS, problem.t_start, problem.t_stop, B, m_p.data(),
-                                                                   m_lbx.data(), m_ubx.data(), num_ineq > 0 ? m_lbg.data() : nullptr,
-                                                                   num_ineq > 0 ? m_ubg.data() : nullptr, nullptr, nullptr, &m_batch);
-            if (st != PMPC_OK) return last_error() = st;
-            if (m_dispatch_mode != 0) { const pmpc_status ds = pmpc_mpc_batch_set_dispatch(m_batch, m_dispatch_mode, m_iter_weight); if (ds != PMPC_OK) return last_error() = ds; }
-        }
         pmpc_sqp_settings ss;
-        pmpc_sqp_settings_default(&ss);
-        ss.tau = m_settings.tau; ss.eta = m_settings.eta; ss.rho = m_settings.rho; ss.eps_prim = m_settings.eps_prim; ss.eps_dual = m_settings.eps_dual;
-        ss.max_iter = m_settings.max_iter; ss.line_search_max_iter = m_settings.line_search_max_iter; ss.regularisation = m_settings.regularisation;
-        ss.exact_hessian_every_iter = m_settings.exact_hessian_every_iter ? 1 : 0; ss.preconditioner = m_settings.preconditioner;
-        ss.hessian_update = m_settings.hessian_update; ss.qp_solver = m_settings.qp_solver;
-        { const pmpc_status fs = filter.bind(ctx, B, m_settings.line_search, ss); if (fs != PMPC_OK) return last_error() = fs; }
+        const pmpc_status st = prepare(ctx, ss);
+        if (st != PMPC_OK) return last_error() = st;
         return last_error() = pmpc_mpc_batch_step(m_batch, x0, &ss, &m_qp_settings, u0, m_info.data());
+    }
+    // The plant of the closed loop (pmpc_mpc_batch_set_plant): the OCP's own dynamics_impl integrated on the device over one control period —
+    // integrator 0 explicit Euler / 1 RK4, 1 .. 64 substeps, control 0 zero-order hold of u(t_start) / 1 the iterate's u(t). d_plant: B * nd static
+    // parameters of the PLANT (model mismatch); nullptr = the controller's. Callable before the first step(). For a registered OCP whose device
+    // library lacks pmpc_user_plant_dev_<DeviceModel> (built before the symbol existed) it returns PMPC_ERR_INVALID_ARGUMENT.
+    static pmpc_plant_settings plant_settings_default() noexcept { pmpc_plant_settings s; pmpc_plant_settings_default(&s); return s; }
+    pmpc_status set_plant(const pmpc_plant_settings& s, const double* d_plant = nullptr) noexcept {
+        if (device_binding<OCP>::registered && !device_binding<OCP>::plant_fn()) return last_error() = PMPC_ERR_INVALID_ARGUMENT;
+        if (m_batch) { const pmpc_status st = pmpc_mpc_batch_set_plant(m_batch, &s, nd > 0 ? d_plant : nullptr, device_binding<OCP>::plant_fn()); if (st != PMPC_OK) return last_error() = st; }
+        else if (s.integrator < 0 || s.integrator > 1 || s.control < 0 || s.control > 1 || s.substeps < 1 || s.substeps > 64 || (s.control == 1 && problem.t_start != 0))
+            return last_error() = PMPC_ERR_INVALID_ARGUMENT;   // (what the batch will be told at its creation)
+        m_plant = s; m_has_plant = true;
+        if (d_plant && nd > 0) m_plant_d.assign(d_plant, d_plant + (size_t)B * nd); else m_plant_d.clear();
+        return last_error() = PMPC_OK;
+    }
+    // K closed-loop steps on the device (pmpc_mpc_batch_rollout): from the states x0 (B * nx), per step [shift the warm start by dt: shift = 1 the
+    // primal iterate, 2 the duals too;] step(); the plant over dt with the additive disturbance w[(b * K + k) * nx + c] (or none). One upload, one
+    // synchronisation, one download: xs[(b * (K + 1) + k) * nx + c], us[(b * K + k) * nu + c], info (optional) [b * K + k]. The same bits as the
+    // loop over step() and plant_step(). info(b) afterwards is that of the last step.
+    pmpc_status rollout(const double* x0, int K, double dt, std::vector<double>& xs, std::vector<double>& us, int shift = 0, const double* w = nullptr,
+                        std::vector<pmpc_sqp_info>* info = nullptr) noexcept {
+        pmpc_context* ctx = context();
+        if (!ctx) return last_error();
+        if (K < 1 || !m_has_plant) return last_error() = PMPC_ERR_INVALID_ARGUMENT;
+        pmpc_sqp_settings ss;
+        const pmpc_status st = prepare(ctx, ss);
+        if (st != PMPC_OK) return last_error() = st;
+        xs.resize((size_t)B * (K + 1) * nx); us.resize((size_t)B * K * nu);
+        std::vector<pmpc_sqp_info> local;
+        std::vector<pmpc_sqp_info>& inf = info ? *info : local;
+        inf.resize((size_t)B * K);
+        const pmpc_status rs = pmpc_mpc_batch_rollout(m_batch, x0, K, dt, shift, &ss, &m_qp_settings, w, xs.data(), us.data(), inf.data());
+        if (rs == PMPC_OK) for (int b = 0; b < B; ++b) m_info[b] = inf[(size_t)b * K + (K - 1)];
+        return last_error() = rs;
+    }
+    // One control period of the plant on host arrays (pmpc_plant_step_batch[_user]): state (B * nx) is advanced in place with the controls u0
+    // (B * nu), the plant settings and parameters of set_plant() and, where the model has parameters or the control is the interpolant, the
+    // batch's current iterate. What rollout() does between two steps.
+    pmpc_status plant_step(double* state, const double* u0, double dt, const double* w = nullptr) noexcept {
+        pmpc_context* ctx = context();
+        if (!ctx) return last_error();
+        if (!m_has_plant) return last_error() = PMPC_ERR_INVALID_ARGUMENT;
+        const double* iterate = nullptr;
+        if (OCP::NP > 0 || m_plant.control == 1) {
+            if (!m_batch) return last_error() = PMPC_ERR_INVALID_ARGUMENT;   // nothing resident before the first step
+            const pmpc_status st = solution(m_iterate);
+            if (st != PMPC_OK) return st;
+            iterate = m_iterate.data();
+        }
+        return last_error() = device_binding<OCP>::plant_step(ctx, problem, OCP::POLY_ORDER, OCP::NUM_SEGMENTS, problem.t_start, problem.t_stop, B, dt, &m_plant, state,
+                                                              u0, iterate, nd > 0 ? (m_plant_d.empty() ? m_p.data() : m_plant_d.data()) : nullptr, w);
     }
     // The setters after the first step() (MPC::set_static_parameters and the bound setters are callable at any time, mpc_wrapper.hpp:103-187):
     // update() uploads what they currently hold (pmpc_mpc_batch_update); the next step() pins its x0 again. Without it a setter called after
@@ -773,12 +813,33 @@ public:
 private:
     double* lbx(int b) noexcept { return &m_lbx[(size_t)b * var_size]; }
     double* ubx(int b) noexcept { return &m_ubx[(size_t)b * var_size]; }
+    // what step() and rollout() share: the batch (created on first use, with the dispatch mode and the plant set before) and the C settings
+    pmpc_status prepare(pmpc_context* ctx, pmpc_sqp_settings& ss) noexcept {
+        if (!m_batch) {
+            const pmpc_status st = device_binding<OCP>::mpc_create(ctx, problem, OCP::POLY_ORDER, OCP::NUM_SEGMENTS, problem.t_start, problem.t_stop, B, m_p.data(),
+                                                                   m_lbx.data(), m_ubx.data(), num_ineq > 0 ? m_lbg.data() : nullptr,
+                                                                   num_ineq > 0 ? m_ubg.data() : nullptr, nullptr, nullptr, &m_batch);
+            if (st != PMPC_OK) return st;
+            if (m_dispatch_mode != 0) { const pmpc_status ds = pmpc_mpc_batch_set_dispatch(m_batch, m_dispatch_mode, m_iter_weight); if (ds != PMPC_OK) return ds; }
+            if (m_has_plant) {
+                const pmpc_status ps = pmpc_mpc_batch_set_plant(m_batch, &m_plant, m_plant_d.empty() ? nullptr : m_plant_d.data(), device_binding<OCP>::plant_fn());
+                if (ps != PMPC_OK) return ps;
+            }
+        }
+        pmpc_sqp_settings_default(&ss);
+        ss.tau = m_settings.tau; ss.eta = m_settings.eta; ss.rho = m_settings.rho; ss.eps_prim = m_settings.eps_prim; ss.eps_dual = m_settings.eps_dual;
+        ss.max_iter = m_settings.max_iter; ss.line_search_max_iter = m_settings.line_search_max_iter; ss.regularisation = m_settings.regularisation;
+        ss.exact_hessian_every_iter = m_settings.exact_hessian_every_iter ? 1 : 0; ss.preconditioner = m_settings.preconditioner;
+        ss.hessian_update = m_settings.hessian_update; ss.qp_solver = m_settings.qp_solver;
+        return filter.bind(ctx, B, m_settings.line_search, ss);
+    }
     OCP problem; int B;
-    std::vector<double> m_lbx, m_ubx, m_lbg, m_ubg, m_p;
+    std::vector<double> m_lbx, m_ubx, m_lbg, m_ubg, m_p, m_plant_d, m_iterate;
     std::vector<pmpc_sqp_info> m_info;
     sqp_settings_t m_settings; qp_solver_settings_t m_qp_settings;
     pmpc_mpc_batch* m_batch{nullptr};
     int m_dispatch_mode{0}, m_iter_weight{default_iter_weight};
+    pmpc_plant_settings m_plant{1, 1, 0}; bool m_has_plant{false};
 public:
     LSFilterHandle filter;   // the solvers' LSFilter members (used when settings().line_search == 1)
 };
@@ -788,6 +849,15 @@ public:
 #define POLYMPC_USE_BUILTIN_OCP(Name, MODEL_ID)                                                                                       \
     template <> struct polympc::device_binding<Name> {                                                                                \
         static constexpr int model_id = MODEL_ID;                                                                                     \
+        static constexpr bool registered = false;                                                                                     \
+        static pmpc_plant_dev_fn plant_fn() { return nullptr; }                                                                       \
+        static pmpc_status plant_step(pmpc_context* ctx, const Name& ocp, int P, int S, double t0, double tf, int B, double dt,       \
+                                      const pmpc_plant_settings* ps, double* state, const double* u0, const double* iterate,          \
+                                      const double* d, const double* w) {                                                             \
+            const std::vector<double> mp = ocp.model_params();                                                                        \
+            return pmpc_plant_step_batch(ctx, MODEL_ID, mp.empty() ? nullptr : mp.data(), (int)mp.size(), P, S, t0, tf, B, dt, ps,    \
+                                         state, u0, iterate, d, w);                                                                   \
+        }                                                                                                                             \
         static pmpc_status solve(pmpc_context* ctx, const Name& ocp, int P, int S, double t0, double tf, int B, const double* xg,     \
                                  const double* lg, const double* d, const double* lbx, const double* ubx, const double* lbg,          \
                                  const double* ubg, const pmpc_sqp_settings* ss, const pmpc_qp_settings* qs, double* x, double* lam,  \
@@ -812,7 +882,20 @@ public:
                                                            const double*, const double*, const double*, const double*, const double*, \
                                                            const double*, const pmpc_sqp_settings*, const pmpc_qp_settings*, double*, \
                                                            double*, pmpc_sqp_info*);                                                  \
+    /* weak: a device library built before the plant symbol existed still links; plant_fn() is then null */                           \
+    extern "C" pmpc_status pmpc_user_plant_dev_##DeviceModel(pmpc_context*, const void*, int, int, double, double, int, double,       \
+                                                             const pmpc_plant_settings*, double*, const double*, const double*,       \
+                                                             const double*, const double*) __attribute__((weak));                     \
     template <> struct polympc::device_binding<Name> {                                                                                \
+        static constexpr bool registered = true;                                                                                      \
+        static pmpc_plant_dev_fn plant_fn() { return &pmpc_user_plant_dev_##DeviceModel; }                                            \
+        static pmpc_status plant_step(pmpc_context* ctx, const Name& ocp, int P, int S, double t0, double tf, int B, double dt,       \
+                                      const pmpc_plant_settings* ps, double* state, const double* u0, const double* iterate,          \
+                                      const double* d, const double* w) {                                                             \
+            const auto dm = ocp.device_model();                                                                                       \
+            return pmpc_plant_step_batch_user(ctx, plant_fn(), &dm, Name::NX, Name::NU, Name::NP, Name::ND, P, S, t0, tf, B, dt, ps,  \
+                                              state, u0, iterate, d, w);                                                              \
+        }                                                                                                                             \
         static pmpc_status solve(pmpc_context* ctx, const Name& ocp, int P, int S, double t0, double tf, int B, const double* xg,     \
                                  const double* lg, const double* d, const double* lbx, const double* ubx, const double* lbg,          \
                                  const double* ubg, const pmpc_sqp_settings* ss, const pmpc_qp_settings* qs, double* x, double* lam,  \
@@ -860,6 +943,13 @@ public:
 }  // namespace models
 template <typename A> struct device_binding<models::MobileRobot<A>> {
     static constexpr int model_id = PMPC_MODEL_ROBOT;   // built-in device code: what BatchSolver's prioritised solve asks for
+    static constexpr bool registered = false;
+    static pmpc_plant_dev_fn plant_fn() { return nullptr; }
+    static pmpc_status plant_step(pmpc_context* ctx, const models::MobileRobot<A>& ocp, int P, int S, double t0, double tf, int B, double dt, const pmpc_plant_settings* ps,
+                                  double* state, const double* u0, const double* iterate, const double* d, const double* w) {
+        const std::vector<double> mp = ocp.model_params();
+        return pmpc_plant_step_batch(ctx, PMPC_MODEL_ROBOT, mp.empty() ? nullptr : mp.data(), (int)mp.size(), P, S, t0, tf, B, dt, ps, state, u0, iterate, d, w);
+    }
     static pmpc_status solve(pmpc_context* ctx, const models::MobileRobot<A>& ocp, int P, int S, double t0, double tf, int B, const double* xg,
                              const double* lg, const double* d, const double* lbx, const double* ubx, const double* lbg, const double* ubg,
                              const pmpc_sqp_settings* ss, const pmpc_qp_settings* qs, double* x, double* lam, pmpc_sqp_info* info) {
@@ -875,6 +965,13 @@ template <typename A> struct device_binding<models::MobileRobot<A>> {
 };
 template <typename A> struct device_binding<models::CSTR<A>> {
     static constexpr int model_id = PMPC_MODEL_CSTR;
+    static constexpr bool registered = false;
+    static pmpc_plant_dev_fn plant_fn() { return nullptr; }
+    static pmpc_status plant_step(pmpc_context* ctx, const models::CSTR<A>& ocp, int P, int S, double t0, double tf, int B, double dt, const pmpc_plant_settings* ps,
+                                  double* state, const double* u0, const double* iterate, const double* d, const double* w) {
+        const std::vector<double> mp = ocp.model_params();
+        return pmpc_plant_step_batch(ctx, PMPC_MODEL_CSTR, mp.empty() ? nullptr : mp.data(), (int)mp.size(), P, S, t0, tf, B, dt, ps, state, u0, iterate, d, w);
+    }
     static pmpc_status solve(pmpc_context* ctx, const models::CSTR<A>&, int P, int S, double t0, double tf, int B, const double* xg,
                              const double* lg, const double* d, const double* lbx, const double* ubx, const double* lbg, const double* ubg,
                              const pmpc_sqp_settings* ss, const pmpc_qp_settings* qs, double* x, double* lam, pmpc_sqp_info* info) {

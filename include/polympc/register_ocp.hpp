@@ -13,11 +13,13 @@
 //
 // compiled with:  hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC -shared my_ocp.hip
 //                       -I<repo>/include -L<repo>/polympc_amd -lpolympc_amd -o libmy_ocp.so
-// This emits the C symbols pmpc_user_sqp_dev_MyOCP (device buffers, type pmpc_sqp_dev_fn) and pmpc_user_dims_MyOCP.
+// This emits the C symbols pmpc_user_sqp_dev_MyOCP (device buffers, type pmpc_sqp_dev_fn), pmpc_user_dims_MyOCP and pmpc_user_plant_dev_MyOCP
+// (type pmpc_plant_dev_fn: one control period of x' = dynamics_impl integrated on the device, the plant of a closed loop — pmpc_plant.hpp).
 // Host code (any C++ compiler) then uses polympc::Solver<...> from <polympc/polympc.hpp> with POLYMPC_USE_REGISTERED_OCP.
 #pragma once
 #include "../polympc_amd.h"
 #include "../../polympc_amd/csrc/pmpc_launch.hpp"
+#include "../../polympc_amd/csrc/pmpc_plant.hpp"
 
 #define PMPC_REGISTER_OCP(Name)                                                                                                  \
     extern "C" pmpc_status pmpc_user_sqp_dev_##Name(pmpc_context* ctx, const void* model, int P, int S, double t0, double tf,   \
@@ -30,4 +32,12 @@
     }                                                                                                                            \
     extern "C" void pmpc_user_dims_##Name(int* nx, int* nu, int* np, int* nd, int* ng) {                                        \
         *nx = Name::NX; *nu = Name::NU; *np = Name::NP; *nd = Name::ND; *ng = Name::NG;                                          \
+    }                                                                                                                            \
+    extern "C" pmpc_status pmpc_user_plant_dev_##Name(pmpc_context* ctx, const void* model, int P, int S, double t0, double tf,  \
+                                                      int B, double dt, const pmpc_plant_settings* settings, double* state,     \
+                                                      const double* u0, const double* iterate, const double* d,                 \
+                                                      const double* w) {                                                        \
+        if (!model) return PMPC_ERR_INVALID_ARGUMENT;                                                                            \
+        return pmpc::plant_launch_dev<Name>(ctx, *static_cast<const Name*>(model), P, S, t0, tf, B, dt, settings, state, u0,     \
+                                            iterate, d, w);                                                                      \
     }

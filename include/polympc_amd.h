@@ -177,7 +177,8 @@ typedef enum {
  * enum values, a trace pointer with a capacity < 1 — with PMPC_ERR_INVALID_ARGUMENT, but a garbage pointer cannot be detected). */
 #define PMPC_ABI_VERSION 4
 int pmpc_abi_version(void);
-/* sizeof of the library's own struct: which = 0 pmpc_qp_settings, 1 pmpc_qp_info, 2 pmpc_sqp_settings, 3 pmpc_sqp_info; 0 for anything else */
+/* sizeof of the library's own struct: which = 0 pmpc_qp_settings, 1 pmpc_qp_info, 2 pmpc_sqp_settings, 3 pmpc_sqp_info, 4 pmpc_plant_settings;
+ * 0 for anything else */
 unsigned long pmpc_struct_size(int which);
 const char* pmpc_version(void);
 const char* pmpc_status_string(pmpc_status s);
@@ -351,7 +352,7 @@ pmpc_status pmpc_iteration_trace_destroy(pmpc_context* ctx, double* trace);
  *      and overwrites them with the new primal / dual solution (Solver::solve() keeps m_x / m_lam between calls),
  *   3. writes the control to apply now, u(t_start) = the last node of the u block, to u0 (B*NU; may be NULL).
  * Device pointers, asynchronous on the context's stream: the plant model / next x0 can be produced on the same stream
- * without any host round trip. */
+ * without any host round trip (pmpc_plant_step_batch_dev below does so with the OCP's own dynamics). */
 pmpc_status pmpc_mpc_step_batch_dev(pmpc_context* ctx, int model, int P, int S, double t0, double tf, const double* mparams,
                                     int n_mparams, int B, const double* x0, const double* d, double* lbx, double* ubx,
                                     const double* lbg, const double* ubg, const pmpc_sqp_settings* sqp_settings,
@@ -505,6 +506,74 @@ pmpc_status pmpc_mpc_batch_create_user(pmpc_context* ctx, pmpc_sqp_dev_fn fn, co
  * carry it. The iterate stays. Nothing calls this implicitly. */
 pmpc_status pmpc_mpc_batch_update(pmpc_mpc_batch* batch, const double* d, const double* lbx, const double* ubx, const double* lbg,
                                   const double* ubg);
+
+/* ---- the plant of a closed loop on the device ------------------------------------------------------------------------------------------
+ * One control period of x' = f(x, u, p, d, t), integrated with the OCP's own dynamics_impl — the built-in models' and, through the symbol
+ * pmpc_user_plant_dev_<Name> that PMPC_REGISTER_OCP emits, a registered OCP's — so that the measured state of the next MPC step is produced on the
+ * context's stream without a host round trip. The model is evaluated with the value-only scalar of the line search (the transcendentals of the
+ * solver kernels). Operation order, fixed, so a result is the same bits whatever the batch or the launch looks like:
+ *   h = dt / substeps
+ *   for s = 0 .. substeps - 1:  ts = (double)s * h
+ *     Euler: k1 = f(x, u(ts), t0 + ts);             x_i = x_i + h * k1_i
+ *     RK4:   k1 = f(x, u(ts), t0 + ts)
+ *            xa_i = x_i + (0.5 * h) * k1_i;         k2 = f(xa, u(ts + 0.5 * h), t0 + (ts + 0.5 * h))
+ *            xb_i = x_i + (0.5 * h) * k2_i;         k3 = f(xb, u(ts + 0.5 * h), t0 + (ts + 0.5 * h))
+ *            xc_i = x_i + h * k3_i;                 k4 = f(xc, u(ts + h), t0 + (ts + h))
+ *            x_i = x_i + (h / 6.0) * (((k1_i + 2.0 * k2_i) + 2.0 * k3_i) + k4_i)
+ *   after the last substep, if w is given: x_i = x_i + w_i
+ * p: the np parameters at the end of the instance's iterate row (the time scaling of the parking models). d: the PLANT's own B * ND static
+ * parameters — they may differ from the controller's (model mismatch). w: B * nx, an additive disturbance the caller generated, or NULL (there
+ * is no device random-number generator). These are new entry points; they do not change PMPC_ABI_VERSION. */
+typedef struct {
+    int integrator;   /* 0 explicit Euler, 1 classical RK4 (default) */
+    int substeps;     /* 1 (default) .. 64 integrator steps per control period */
+    int control;      /* 0 (default) zero-order hold of the given u0; 1 the interpolant u(tau) of the instance's iterate at the horizon-relative
+                       * time tau (the operation of pmpc_traj_sample_batch_dev) — t0 must then be 0, as for the shift */
+} pmpc_plant_settings;
+void pmpc_plant_settings_default(pmpc_plant_settings* s);   /* RK4, 1 substep, control 0; pmpc_struct_size(4) is the library's sizeof */
+
+/* state (B * nx) is advanced by dt IN PLACE. u0: B * nu, read when control == 0 (may be NULL otherwise). iterate: B * n rows in the OCP variable
+ * layout; may be NULL when np == 0 and control == 0. (P, S, t0, tf): the controller's grid. Device pointers, asynchronous on the context's stream.
+ * Refused before any device call — PMPC_ERR_INVALID_ARGUMENT: a NULL ctx, settings or state; B < 0; u0 NULL with control == 0; iterate NULL with
+ * np > 0 or control == 1; d NULL with ND > 0; dt not finite or <= 0; substeps outside 1 .. 64; an unknown integrator or control; control == 1 with
+ * t0 != 0; t0 / tf not finite or tf <= t0. PMPC_ERR_UNKNOWN_MODEL; PMPC_ERR_UNSUPPORTED_SIZE for a grid beyond P <= 15, P * S + 1 <= 64 (as the
+ * trajectory entries). B == 0: nothing is done. mparams: as for pmpc_sqp_solve_batch (the dynamics of the built-in models read none). */
+pmpc_status pmpc_plant_step_batch_dev(pmpc_context* ctx, int model, const double* mparams, int n_mparams, int P, int S, double t0, double tf, int B,
+                                      double dt, const pmpc_plant_settings* settings, double* state, const double* u0, const double* iterate,
+                                      const double* d, const double* w);
+/* The same with host buffers: state is copied up, advanced and copied back; the call synchronises. */
+pmpc_status pmpc_plant_step_batch(pmpc_context* ctx, int model, const double* mparams, int n_mparams, int P, int S, double t0, double tf, int B,
+                                  double dt, const pmpc_plant_settings* settings, double* state, const double* u0, const double* iterate,
+                                  const double* d, const double* w);
+/* A registered OCP's plant on device buffers: the symbol pmpc_user_plant_dev_<Name>; `model` points to the user's model object (copied by value
+ * into the kernel). The two entries below take it with the OCP's dimensions, as pmpc_mpc_step_batch_user_dev does, on device resp. host buffers;
+ * refusals as above, and a NULL fn or model, nx < 1, nu, np or nd < 0. A status returned by fn is passed through. */
+typedef pmpc_status (*pmpc_plant_dev_fn)(pmpc_context* ctx, const void* model, int P, int S, double t0, double tf, int B, double dt,
+                                         const pmpc_plant_settings* settings, double* state, const double* u0, const double* iterate,
+                                         const double* d, const double* w);
+pmpc_status pmpc_plant_step_batch_user_dev(pmpc_context* ctx, pmpc_plant_dev_fn fn, const void* model, int nx, int nu, int np, int nd, int P, int S,
+                                           double t0, double tf, int B, double dt, const pmpc_plant_settings* settings, double* state,
+                                           const double* u0, const double* iterate, const double* d, const double* w);
+pmpc_status pmpc_plant_step_batch_user(pmpc_context* ctx, pmpc_plant_dev_fn fn, const void* model, int nx, int nu, int np, int nd, int P, int S,
+                                       double t0, double tf, int B, double dt, const pmpc_plant_settings* settings, double* state,
+                                       const double* u0, const double* iterate, const double* d, const double* w);
+
+/* The plant of an opaque batch, of either kind. settings are copied. d_plant: B * ND host values, uploaded once; NULL = the plant reads the
+ * controller's d (also after a later pmpc_mpc_batch_update). plant_fn: NULL for a built-in batch, the registered OCP's pmpc_user_plant_dev_<Name>
+ * for a registered one. PMPC_ERR_INVALID_ARGUMENT before any device call: a NULL batch or settings, substeps outside 1 .. 64, an unknown
+ * integrator or control, control == 1 on a batch whose horizon does not start at 0, a registered batch without plant_fn, a built-in batch with one. */
+pmpc_status pmpc_mpc_batch_set_plant(pmpc_mpc_batch* batch, const pmpc_plant_settings* settings, const double* d_plant, pmpc_plant_dev_fn plant_fn);
+/* K closed-loop steps, enqueued as a whole on the context's stream: one upload (x0_init B * nx, w), one synchronisation, one download. Per step
+ * k = 0 .. K - 1: xs[k] <- the state; if k > 0 and shift != 0 the warm start moves forward by dt (pmpc_mpc_batch_shift; shift = 1 the primal
+ * iterate, 2 the duals too); the MPC step in the batch's dispatch mode, through the entry points pmpc_mpc_batch_step uses; us[k] <- u(t_start),
+ * info[k] <- the step's info; the plant advances the state by dt with u0 = us[k], the batch's iterate and w[k]. Then xs[K] <- the state.
+ * Host arrays: xs[(b * (K + 1) + k) * nx + c], us[(b * K + k) * nu + c], info[b * K + k] (may be NULL), w[(b * K + k) * nx + c] (may be NULL).
+ * The result is what the same calls give when a host drives them step by step, bit for bit. No early termination. PMPC_ERR_INVALID_ARGUMENT
+ * before any device call: a NULL batch, x0_init, settings, xs or us; K < 1; dt not finite or <= 0; shift outside 0 .. 2, or != 0 on a horizon that
+ * does not start at 0; no pmpc_mpc_batch_set_plant before; and what the step itself refuses in the settings (max_iter < 1, a regularisation or
+ * kkt_form outside 0 .. 2, a trace without capacity, filter_state / iteration_trace in dispatch mode 1). */
+pmpc_status pmpc_mpc_batch_rollout(pmpc_mpc_batch* batch, const double* x0_init, int K, double dt, int shift, const pmpc_sqp_settings* sqp_settings,
+                                   const pmpc_qp_settings* qp_settings, const double* w, double* xs, double* us, pmpc_sqp_info* info);
 
 /* ---- generic NLPs ----------------------------------------------------------------------------------------------------
  * Batched SQPBase::solve for NLPs that are not collocation OCPs: the reference's ProblemBase problems (src/solvers/nlproblem.hpp), with

@@ -12,4 +12,5 @@ from .capi import (  # noqa: F401
     MODEL_ROBOT, MODEL_CSTR, MODEL_PARKING, MODEL_ROBOT_NG, MODEL_KITE_STANDIN, MODEL_PARKING_NG,
     QP_SOLVED, QP_MAX_ITER_EXCEEDED, SQP_SOLVED, SQP_MAX_ITER_EXCEEDED, EXPORTED_SYMBOLS,
     NLP_CONSTRAINED_ROSENBROCK, NLP_ROSENBROCK, NLP_SIMPLE, NLP_HS071, StatusError, UserNLP, nlp_dims, UserOCP, MPCBatch,
+    PlantSettings, plant_settings_default,
 )

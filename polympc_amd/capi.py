@@ -35,6 +35,8 @@ EXPORTED_SYMBOLS = [
     "pmpc_mpc_step_batch_prioritised_dev", "pmpc_mpc_batch_set_dispatch",
     "pmpc_traj_sample_batch", "pmpc_traj_sample_batch_dev", "pmpc_traj_shift_batch_dev", "pmpc_traj_regrid_batch", "pmpc_traj_regrid_batch_dev",
     "pmpc_mpc_batch_sample", "pmpc_mpc_batch_shift",
+    "pmpc_plant_settings_default", "pmpc_plant_step_batch", "pmpc_plant_step_batch_dev", "pmpc_plant_step_batch_user", "pmpc_plant_step_batch_user_dev",
+    "pmpc_mpc_batch_set_plant", "pmpc_mpc_batch_rollout",
     "pmpc_qp_admm_solve_batch", "pmpc_qp_admm_solve_batch_dev", "pmpc_qp_ruiz_compute_batch", "pmpc_qp_ruiz_compute_batch_dev", "pmpc_qp_ruiz_unscale_batch", "pmpc_qp_ruiz_unscale_batch_dev",
     "pmpc_filter_state_create", "pmpc_filter_state_clear", "pmpc_filter_state_download", "pmpc_filter_state_destroy",
     "pmpc_iteration_trace_create", "pmpc_iteration_trace_clear", "pmpc_iteration_trace_download", "pmpc_iteration_trace_destroy",
@@ -72,6 +74,14 @@ class SQPInfo(C.Structure):
                 ("primal_norm", C.c_double), ("dual_norm", C.c_double), ("max_violation", C.c_double),
                 ("cost", C.c_double)]
 
+
+class PlantSettings(C.Structure):
+    """pmpc_plant_settings: integrator 0 explicit Euler / 1 RK4, substeps 1 .. 64, control 0 zero-order hold of u0 / 1 the iterate's u(tau)"""
+    _fields_ = [("integrator", C.c_int), ("substeps", C.c_int), ("control", C.c_int)]
+
+
+INTEGRATOR_EULER, INTEGRATOR_RK4 = 0, 1
+CONTROL_HOLD, CONTROL_INTERPOLANT = 0, 1
 
 QP_INFO_DTYPE = np.dtype([("status", "i4"), ("iter", "i4"), ("rho_updates", "i4"), ("flags", "i4"),
                           ("rho_estimate", "f8"), ("res_prim", "f8"), ("res_dual", "f8")])
@@ -158,6 +168,15 @@ def qp_settings_sqp_default():
 
 def sqp_settings_default():
     s = SQPSettings(); lib().pmpc_sqp_settings_default(C.byref(s)); return s
+
+
+def plant_settings_default(integrator=None, substeps=None, control=None):
+    """pmpc_plant_settings_default (RK4, 1 substep, zero-order hold), then the given fields"""
+    s = PlantSettings(); lib().pmpc_plant_settings_default(C.byref(s))
+    for name, v in (("integrator", integrator), ("substeps", substeps), ("control", control)):
+        if v is not None:
+            setattr(s, name, int(v))
+    return s
 
 
 def chebyshev(P):
@@ -248,6 +267,7 @@ class UserOCP:
         lib()   # loaded first: the user's library finds the product library it was linked against by its soname, wherever it lies
         self.so = C.CDLL(os.path.abspath(so_path))
         self.fn = getattr(self.so, "pmpc_user_sqp_dev_" + name)
+        self.name, self._plant_fn = name, None
         v = [C.c_int() for _ in range(5)]
         getattr(self.so, "pmpc_user_dims_" + name)(*[C.byref(a) for a in v])
         self.nx, self.nu, self.np, self.nd, self.ng = [a.value for a in v]
@@ -292,6 +312,33 @@ class UserOCP:
         _check_status(f(*self._head(ctx), *self._grid(P, S, t0, tf), int(B), _d(x0), _d(d), _d(lbx), _d(ubx), _d(lbg), _d(ubg), C.byref(sqp_settings),
                         C.byref(qp_settings), _d(x), _d(lam), C.c_void_p(info.data_ptr()), _d(u0), _dv(priority), int(iter_weight)))
 
+    @property
+    def plant_fn(self):
+        """pmpc_user_plant_dev_<name>, looked up when a plant is first used: a user library built before the symbol existed keeps loading"""
+        if self._plant_fn is None:
+            try:
+                self._plant_fn = getattr(self.so, "pmpc_user_plant_dev_" + self.name)
+            except AttributeError:
+                raise RuntimeError(f"the library of the registered OCP {self.name} has no pmpc_user_plant_dev_{self.name}: rebuild it "
+                                   "against this include/polympc/register_ocp.hpp") from None
+        return self._plant_fn
+
+    def _plant_call(self, f, ctx, P, S, t0, tf, B, dt, settings, ptrs):
+        f.argtypes = _USER_OCP_HEAD + [C.c_int] * 6 + [C.c_double] * 2 + [C.c_int, C.c_double, C.POINTER(PlantSettings)] + [C.POINTER(C.c_double)] * 5
+        _check_status(f(ctx._ctx, C.cast(self.plant_fn, C.c_void_p), C.cast(self.model, C.c_void_p), self.nx, self.nu, self.np, self.nd, int(P), int(S),
+                        float(t0), float(tf), int(B), float(dt), C.byref(settings or plant_settings_default()), *ptrs))
+
+    def plant_step_batch(self, ctx, P, S, t0, tf, dt, state, u0=None, iterate=None, d=None, w=None, settings=None):
+        """pmpc_plant_step_batch_user (host buffers): state (B, nx) advanced by dt -> a new array"""
+        sk = np.array(np.atleast_2d(state), dtype=np.float64, order="C")
+        keep = [_h(a) for a in (u0, iterate, d, w)]
+        self._plant_call(lib().pmpc_plant_step_batch_user, ctx, P, S, t0, tf, sk.shape[0], dt, settings, [_h(sk)[1]] + [k[1] for k in keep])
+        return sk
+
+    def plant_step_batch_dev(self, ctx, P, S, t0, tf, B, dt, state, u0=None, iterate=None, d=None, w=None, settings=None):
+        """pmpc_plant_step_batch_user_dev on torch CUDA tensors: state (B, nx) advanced in place; asynchronous on the context's stream"""
+        self._plant_call(lib().pmpc_plant_step_batch_user_dev, ctx, P, S, t0, tf, B, dt, settings, [_d(a) for a in (state, u0, iterate, d, w)])
+
     def mpc_batch(self, ctx, P, S, t0, tf, B, d, lbx, ubx, lbg=None, ubg=None, x_guess=None, lam_guess=None):
         """pmpc_mpc_batch_create_user: B controllers of this OCP whose data stay on the device between steps (MPCBatch)"""
         return MPCBatch(ctx, self, P, S, t0, tf, B, d, lbx, ubx, lbg, ubg, x_guess, lam_guess)
@@ -329,6 +376,7 @@ class MPCBatch:
         model object)"""
         self.B = int(B)
         self._batch = C.c_void_p()
+        self._user = model if isinstance(model, UserOCP) else None
         P_ = C.POINTER(C.c_double)
         if isinstance(model, UserOCP):
             self.dims = model.dims(P, S)
@@ -399,6 +447,31 @@ class MPCBatch:
         f = lib().pmpc_mpc_batch_shift
         f.argtypes = [C.c_void_p, C.c_double, C.c_int]
         _check_status(f(self._batch, float(dt), 1 if duals else 0))
+
+    def set_plant(self, settings=None, d_plant=None):
+        """pmpc_mpc_batch_set_plant: the plant of rollout() — settings (default: RK4, 1 substep, zero-order hold) and the plant's own static
+        parameters (B, nd), None = the controller's; a registered OCP's batch passes its pmpc_user_plant_dev_<name>"""
+        dk, dp = _h(d_plant)
+        assert dk is None or dk.size == self.B * self.dims["nd"], "d_plant of another size than the batch's static parameters"
+        f = lib().pmpc_mpc_batch_set_plant
+        f.argtypes = [C.c_void_p, C.POINTER(PlantSettings), C.POINTER(C.c_double), C.c_void_p]
+        _check_status(f(self._batch, C.byref(settings or plant_settings_default()), dp,
+                        C.cast(self._user.plant_fn, C.c_void_p) if self._user is not None else None))
+
+    def rollout(self, x0, K, dt, sqp_settings, qp_settings, shift=0, w=None):
+        """pmpc_mpc_batch_rollout: K closed-loop steps on the device from the states x0 (B, nx); shift 0 none / 1 the primal warm start / 2 the duals
+        too; w (B, K, nx): additive disturbances or None -> xs (B, K + 1, nx), us (B, K, nu), info (B, K)"""
+        K = int(K)
+        xk, xp = _h(x0); wk, wp = _h(w)
+        assert xk.size == self.B * self.dims["nx"] and (wk is None or wk.size == self.B * K * self.dims["nx"])
+        xs = np.zeros((self.B, max(K, 0) + 1, self.dims["nx"])); us = np.zeros((self.B, max(K, 0), self.dims["nu"]))
+        info = np.zeros((self.B, max(K, 0)), dtype=SQP_INFO_DTYPE)
+        P_ = C.POINTER(C.c_double)
+        f = lib().pmpc_mpc_batch_rollout
+        f.argtypes = [C.c_void_p, P_, C.c_int, C.c_double, C.c_int, C.POINTER(SQPSettings), C.POINTER(QPSettings), P_, P_, P_, C.c_void_p]
+        _check_status(f(self._batch, xp, K, float(dt), int(shift), C.byref(sqp_settings), C.byref(qp_settings), wp, xs.ctypes.data_as(P_),
+                        us.ctypes.data_as(P_), C.c_void_p(info.ctypes.data)))
+        return xs, us, info
 
     def close(self):
         if self._batch:
@@ -710,6 +783,31 @@ class Context:
         f = lib().pmpc_traj_regrid_batch_dev
         f.argtypes = self._TRAJ_REGRID_ARGTYPES
         _check_status(f(self._ctx, int(B), nx, nu, np_, P, S, P2, S2, t0, tf, _d(x_src), _d(x_dst)))
+
+    # ------------------------------------------------------------------ the plant of a closed loop (pmpc_plant_*)
+    _PLANT_ARGTYPES = [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_double,
+                       C.POINTER(PlantSettings)] + [C.POINTER(C.c_double)] * 5
+
+    def plant_step_batch(self, model, P, S, t0, tf, dt, state, u0=None, iterate=None, d=None, w=None, settings=None, mparams=None):
+        """pmpc_plant_step_batch (host buffers): state (B, nx) advanced by one control period dt with the model's own dynamics -> a new array.
+        u0 (B, nu) for control 0; iterate (B, n) when the model has parameters or for control 1; d (B, nd): the PLANT's static parameters;
+        w (B, nx): an additive disturbance"""
+        sk = np.array(np.atleast_2d(state), dtype=np.float64, order="C")
+        mk, mp = _h(mparams)
+        keep = [_h(a) for a in (u0, iterate, d, w)]
+        f = lib().pmpc_plant_step_batch
+        f.argtypes = self._PLANT_ARGTYPES
+        _check_status(f(self._ctx, int(model), mp, 0 if mk is None else len(mk), int(P), int(S), float(t0), float(tf), sk.shape[0], float(dt),
+                        C.byref(settings or plant_settings_default()), _h(sk)[1], *[k[1] for k in keep]))
+        return sk
+
+    def plant_step_batch_dev(self, model, P, S, t0, tf, B, dt, state, u0=None, iterate=None, d=None, w=None, settings=None, mparams=None):
+        """pmpc_plant_step_batch_dev on torch CUDA tensors: state (B, nx) advanced in place; asynchronous on the context's stream"""
+        mk, mp = _h(mparams)
+        f = lib().pmpc_plant_step_batch_dev
+        f.argtypes = self._PLANT_ARGTYPES
+        _check_status(f(self._ctx, int(model), mp, 0 if mk is None else len(mk), int(P), int(S), float(t0), float(tf), int(B), float(dt),
+                        C.byref(settings or plant_settings_default()), _d(state), _d(u0), _d(iterate), _d(d), _d(w)))
 
     def mpc_batch(self, model, P, S, t0, tf, B, d, lbx, ubx, lbg=None, ubg=None, x_guess=None, lam_guess=None, mparams=None):
         """pmpc_mpc_batch_create: B controllers whose data stay on the device between steps (MPCBatch)"""

@@ -56,6 +56,7 @@ unsigned long pmpc_struct_size(int which) {
         case 1: return (unsigned long)sizeof(pmpc_qp_info);
         case 2: return (unsigned long)sizeof(pmpc_sqp_settings);
         case 3: return (unsigned long)sizeof(pmpc_sqp_info);
+        case 4: return (unsigned long)sizeof(pmpc_plant_settings);
     }
     return 0;
 }
@@ -396,12 +397,15 @@ struct pmpc_mpc_batch {
     double *d = nullptr, *lbx = nullptr, *ubx = nullptr, *lbg = nullptr, *ubg = nullptr, *x = nullptr, *lam = nullptr, *x0 = nullptr, *u0 = nullptr;
     pmpc_sqp_info* info = nullptr;
     int dispatch_mode = 0, iter_weight = 0; int* priority = nullptr; bool stepped = false;   // pmpc_mpc_batch_set_dispatch
+    bool has_plant = false; pmpc_plant_settings plant{}; pmpc_plant_dev_fn plant_fn = nullptr; double* d_plant = nullptr;   // pmpc_mpc_batch_set_plant
+    void* roll[5] = {nullptr}; size_t roll_bytes[5] = {0};   // pmpc_mpc_batch_rollout: xs, us, info, w and the w of one step; they only grow
 };
 pmpc_status pmpc_mpc_batch_destroy(pmpc_mpc_batch* h) {
     if (!h) return PMPC_ERR_INVALID_ARGUMENT;
     (void)hipSetDevice(h->ctx->device);
     (void)hipStreamSynchronize(h->ctx->stream);
-    for (void* q : {(void*)h->d, (void*)h->lbx, (void*)h->ubx, (void*)h->lbg, (void*)h->ubg, (void*)h->x, (void*)h->lam, (void*)h->x0, (void*)h->u0, (void*)h->info, (void*)h->priority})
+    for (void* q : {(void*)h->d, (void*)h->lbx, (void*)h->ubx, (void*)h->lbg, (void*)h->ubg, (void*)h->x, (void*)h->lam, (void*)h->x0, (void*)h->u0, (void*)h->info, (void*)h->priority, (void*)h->d_plant,
+                    h->roll[0], h->roll[1], h->roll[2], h->roll[3], h->roll[4]})
         if (q) (void)hipFree(q);
     delete h;
     return PMPC_OK;
@@ -460,25 +464,28 @@ pmpc_status pmpc_mpc_batch_create_user(pmpc_context* ctx, pmpc_sqp_dev_fn fn, co
     return mpc_batch_create(ctx, DevSolver{0, nullptr, 0, fn, model, P, S, t0, tf}, (size_t)model_bytes, user_sizes(nx, nu, np, nd, ng, P, S), B, d, lbx,
                             ubx, lbg, ubg, x_guess, lam_guess, out);
 }
+// The step of an opaque batch on its resident x0, in its dispatch mode — through the public entry points: their argument checks are the step's.
+static pmpc_status mpc_batch_step_dev(pmpc_mpc_batch* h, const pmpc_sqp_settings* ss, const pmpc_qp_settings* qs) {
+    pmpc_context* ctx = h->ctx;
+    const DevSolver& sv = h->solve;
+    const OcpSizes& z = h->z;
+    if (sv.fn)
+        return pmpc_mpc_step_batch_user_dev(ctx, sv.fn, sv.user, z.nx, z.nu, z.np, z.nd, z.ng, sv.P, sv.S, sv.t0, sv.tf, h->B, h->x0, h->d, h->lbx, h->ubx, h->lbg,
+                                            h->ubg, ss, qs, h->x, h->lam, h->info, h->u0, h->dispatch_mode == 1 ? h->priority : nullptr, h->iter_weight);
+    if (h->dispatch_mode == 1)
+        return pmpc_mpc_step_batch_prioritised_dev(ctx, sv.model, sv.P, sv.S, sv.t0, sv.tf, sv.mparams, sv.n_mparams, h->B, h->x0, h->d, h->lbx, h->ubx, h->lbg,
+                                                   h->ubg, ss, qs, h->x, h->lam, h->info, h->u0, h->priority, h->iter_weight);
+    return pmpc_mpc_step_batch_dev(ctx, sv.model, sv.P, sv.S, sv.t0, sv.tf, sv.mparams, sv.n_mparams, h->B, h->x0, h->d, h->lbx, h->ubx, h->lbg, h->ubg,
+                                   ss, qs, h->x, h->lam, h->info, h->u0);
+}
 pmpc_status pmpc_mpc_batch_step(pmpc_mpc_batch* h, const double* x0, const pmpc_sqp_settings* ss, const pmpc_qp_settings* qs, double* u0,
                                 pmpc_sqp_info* info) {
     if (!h || !x0 || !ss || !qs) return PMPC_ERR_INVALID_ARGUMENT;
     pmpc_context* ctx = h->ctx;
-    const DevSolver& sv = h->solve;
     const OcpSizes& z = h->z;
     HIPCHK(hipSetDevice(ctx->device));
     HIPCHK(hipMemcpyAsync(h->x0, x0, (size_t)h->B * z.nx * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    // through the public entry points: their argument checks are the step's
-    pmpc_status st;
-    if (sv.fn)
-        st = pmpc_mpc_step_batch_user_dev(ctx, sv.fn, sv.user, z.nx, z.nu, z.np, z.nd, z.ng, sv.P, sv.S, sv.t0, sv.tf, h->B, h->x0, h->d, h->lbx, h->ubx, h->lbg,
-                                          h->ubg, ss, qs, h->x, h->lam, h->info, h->u0, h->dispatch_mode == 1 ? h->priority : nullptr, h->iter_weight);
-    else if (h->dispatch_mode == 1)
-        st = pmpc_mpc_step_batch_prioritised_dev(ctx, sv.model, sv.P, sv.S, sv.t0, sv.tf, sv.mparams, sv.n_mparams, h->B, h->x0, h->d, h->lbx, h->ubx, h->lbg,
-                                                 h->ubg, ss, qs, h->x, h->lam, h->info, h->u0, h->priority, h->iter_weight);
-    else
-        st = pmpc_mpc_step_batch_dev(ctx, sv.model, sv.P, sv.S, sv.t0, sv.tf, sv.mparams, sv.n_mparams, h->B, h->x0, h->d, h->lbx, h->ubx, h->lbg, h->ubg,
-                                     ss, qs, h->x, h->lam, h->info, h->u0);
+    const pmpc_status st = mpc_batch_step_dev(h, ss, qs);
     if (st != PMPC_OK) return st;
     h->stepped = true;
     if (u0) HIPCHK(hipMemcpyAsync(u0, h->u0, (size_t)h->B * z.nu * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
@@ -672,6 +679,100 @@ pmpc_status pmpc_mpc_batch_shift(pmpc_mpc_batch* h, double dt, int shift_duals) 
     if (!h || !(dt >= 0.0 && dt <= 1.7976931348623157e308)) return PMPC_ERR_INVALID_ARGUMENT;   // (a bad dt is refused before the handle is read)
     const OcpSizes& z = h->z;
     return pmpc_traj_shift_batch_dev(h->ctx, h->B, z.nx, z.nu, z.np, z.ng, h->solve.P, h->solve.S, h->solve.t0, h->solve.tf, dt, h->x, shift_duals ? h->lam : nullptr);
+}
+
+/* ---- the plant of an opaque batch and the closed-loop rollout (the plant kernel and the pmpc_plant_* entries: pmpc_plant.hip) ---- */
+static bool plant_settings_ok(const pmpc_plant_settings* s) {
+    return s && (s->integrator == 0 || s->integrator == 1) && (s->control == 0 || s->control == 1) && s->substeps >= 1 && s->substeps <= 64;
+}
+pmpc_status pmpc_mpc_batch_set_plant(pmpc_mpc_batch* h, const pmpc_plant_settings* settings, const double* d_plant, pmpc_plant_dev_fn plant_fn) {
+    if (!h || !plant_settings_ok(settings)) return PMPC_ERR_INVALID_ARGUMENT;
+    if ((settings->control == 1 && h->solve.t0 != 0.0) || (h->solve.fn != nullptr) != (plant_fn != nullptr)) return PMPC_ERR_INVALID_ARGUMENT;
+    pmpc_context* ctx = h->ctx;
+    const size_t bytes = (size_t)h->B * h->z.nd * sizeof(double);
+    if (d_plant && bytes) {
+        HIPCHK(hipSetDevice(ctx->device));
+        if (!h->d_plant) HIPCHK(hipMalloc((void**)&h->d_plant, bytes));
+        HIPCHK(hipMemcpyAsync(h->d_plant, d_plant, bytes, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+    } else if (h->d_plant) {   // back to the controller's d
+        HIPCHK(hipSetDevice(ctx->device));
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        HIPCHK(hipFree(h->d_plant));
+        h->d_plant = nullptr;
+    }
+    h->plant = *settings; h->plant_fn = plant_fn; h->has_plant = true;
+    return PMPC_OK;
+}
+
+// dst[b * dst_stride + c] = src[b * src_stride + c], c < words: the recording copies of a rollout (64-bit words; the strides in words)
+__global__ void mpc_record_kernel(int B, int words, const unsigned long long* __restrict__ src, size_t src_stride, unsigned long long* __restrict__ dst,
+                                  size_t dst_stride) {
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (size_t)B * words) return;
+    const size_t b = idx / words, c = idx - b * words;
+    dst[b * dst_stride + c] = src[b * src_stride + c];
+}
+static pmpc_status mpc_record(pmpc_context* ctx, int B, size_t words, const void* src, size_t src_stride, void* dst, size_t dst_stride) {
+    if (words == 0) return PMPC_OK;
+    hipLaunchKernelGGL(mpc_record_kernel, dim3((unsigned)(((size_t)B * words + 255) / 256)), dim3(256), 0, ctx->stream, B, (int)words,
+                       (const unsigned long long*)src, src_stride, (unsigned long long*)dst, dst_stride);
+    HIPCHK(hipGetLastError());
+    return PMPC_OK;
+}
+
+pmpc_status pmpc_mpc_batch_rollout(pmpc_mpc_batch* h, const double* x0_init, int K, double dt, int shift, const pmpc_sqp_settings* ss,
+                                   const pmpc_qp_settings* qs, const double* w, double* xs, double* us, pmpc_sqp_info* info) {
+    if (!h || !x0_init || !ss || !qs || !xs || !us || K < 1 || shift < 0 || shift > 2) return PMPC_ERR_INVALID_ARGUMENT;
+    if (!(dt > 0.0 && dt <= 1.7976931348623157e308) || !h->has_plant || (shift != 0 && h->solve.t0 != 0.0)) return PMPC_ERR_INVALID_ARGUMENT;
+    // what the step refuses in the settings, asked here so that nothing is enqueued before a refusal
+    if (ss->max_iter < 1 || ss->regularisation < 0 || ss->regularisation > 2 || ss->kkt_form < 0 || ss->kkt_form > 2 ||
+        (ss->iteration_trace && ss->iteration_trace_capacity < 1) || (h->dispatch_mode == 1 && has_positional_state(ss)))
+        return PMPC_ERR_INVALID_ARGUMENT;
+    pmpc_context* ctx = h->ctx;
+    const DevSolver& sv = h->solve;
+    const OcpSizes& z = h->z;
+    const int B = h->B;
+    const size_t Bz = (size_t)B, Kz = (size_t)K, nx = (size_t)z.nx, nu = (size_t)z.nu, iw = sizeof(pmpc_sqp_info) / sizeof(unsigned long long);
+    if (Bz * (Kz + 1) * nx > (size_t)0x7fffffff || Bz * Kz * iw > (size_t)0x7fffffff) return PMPC_ERR_UNSUPPORTED_SIZE;   // (the recording kernel's grid)
+    HIPCHK(hipSetDevice(ctx->device));
+    const size_t want[5] = {Bz * (Kz + 1) * nx * sizeof(double), Bz * Kz * nu * sizeof(double), Bz * Kz * sizeof(pmpc_sqp_info),
+                            w ? Bz * Kz * nx * sizeof(double) : 0, w ? Bz * nx * sizeof(double) : 0};
+    for (int i = 0; i < 5; ++i)
+        if (h->roll_bytes[i] < want[i]) {
+            HIPCHK(hipStreamSynchronize(ctx->stream));
+            if (h->roll[i]) HIPCHK(hipFree(h->roll[i]));
+            h->roll[i] = nullptr; h->roll_bytes[i] = 0;
+            HIPCHK(hipMalloc(&h->roll[i], want[i]));
+            h->roll_bytes[i] = want[i];
+        }
+    double *dxs = (double*)h->roll[0], *dus = (double*)h->roll[1], *dw = w ? (double*)h->roll[3] : nullptr, *wk = w ? (double*)h->roll[4] : nullptr;
+    pmpc_sqp_info* dinfo = (pmpc_sqp_info*)h->roll[2];
+    HIPCHK(hipMemcpyAsync(h->x0, x0_init, Bz * nx * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    if (w) HIPCHK(hipMemcpyAsync(dw, w, want[3], hipMemcpyHostToDevice, ctx->stream));
+    const double* dpl = h->d_plant ? h->d_plant : h->d;
+    pmpc_status st;
+    for (size_t k = 0; k < Kz; ++k) {
+        if ((st = mpc_record(ctx, B, nx, h->x0, nx, dxs + k * nx, (Kz + 1) * nx)) != PMPC_OK) return st;
+        if (k > 0 && shift != 0 &&
+            (st = pmpc_traj_shift_batch_dev(ctx, B, z.nx, z.nu, z.np, z.ng, sv.P, sv.S, sv.t0, sv.tf, dt, h->x, shift == 2 ? h->lam : nullptr)) != PMPC_OK)
+            return st;
+        if ((st = mpc_batch_step_dev(h, ss, qs)) != PMPC_OK) return st;
+        h->stepped = true;
+        if ((st = mpc_record(ctx, B, nu, h->u0, nu, dus + k * nu, Kz * nu)) != PMPC_OK) return st;
+        if ((st = mpc_record(ctx, B, iw, h->info, iw, dinfo + k, Kz * iw)) != PMPC_OK) return st;
+        if (w && (st = mpc_record(ctx, B, nx, dw + k * nx, Kz * nx, wk, nx)) != PMPC_OK) return st;
+        st = sv.fn ? pmpc_plant_step_batch_user_dev(ctx, h->plant_fn, sv.user, z.nx, z.nu, z.np, z.nd, sv.P, sv.S, sv.t0, sv.tf, B, dt, &h->plant, h->x0, h->u0,
+                                                    h->x, dpl, wk)
+                   : pmpc_plant_step_batch_dev(ctx, sv.model, sv.mparams, sv.n_mparams, sv.P, sv.S, sv.t0, sv.tf, B, dt, &h->plant, h->x0, h->u0, h->x, dpl, wk);
+        if (st != PMPC_OK) return st;
+    }
+    if ((st = mpc_record(ctx, B, nx, h->x0, nx, dxs + Kz * nx, (Kz + 1) * nx)) != PMPC_OK) return st;
+    HIPCHK(hipMemcpyAsync(xs, dxs, want[0], hipMemcpyDeviceToHost, ctx->stream));
+    if (nu) HIPCHK(hipMemcpyAsync(us, dus, want[1], hipMemcpyDeviceToHost, ctx->stream));
+    if (info) HIPCHK(hipMemcpyAsync(info, dinfo, want[2], hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return PMPC_OK;
 }
 
 /* contiguous shards over n_ctx contexts, one PERSISTENT host thread per context (started on the context's first sharded call, joined
