@@ -846,34 +846,31 @@ public:
 
 // ---------------------------------------------------------------------------------------------------------------------
 // device bindings
-#define POLYMPC_USE_BUILTIN_OCP(Name, MODEL_ID)                                                                                       \
-    template <> struct polympc::device_binding<Name> {                                                                                \
-        static constexpr int model_id = MODEL_ID;                                                                                     \
-        static constexpr bool registered = false;                                                                                     \
-        static pmpc_plant_dev_fn plant_fn() { return nullptr; }                                                                       \
-        static pmpc_status plant_step(pmpc_context* ctx, const Name& ocp, int P, int S, double t0, double tf, int B, double dt,       \
-                                      const pmpc_plant_settings* ps, double* state, const double* u0, const double* iterate,          \
-                                      const double* d, const double* w) {                                                             \
-            const std::vector<double> mp = ocp.model_params();                                                                        \
-            return pmpc_plant_step_batch(ctx, MODEL_ID, mp.empty() ? nullptr : mp.data(), (int)mp.size(), P, S, t0, tf, B, dt, ps,    \
-                                         state, u0, iterate, d, w);                                                                   \
-        }                                                                                                                             \
-        static pmpc_status solve(pmpc_context* ctx, const Name& ocp, int P, int S, double t0, double tf, int B, const double* xg,     \
-                                 const double* lg, const double* d, const double* lbx, const double* ubx, const double* lbg,          \
-                                 const double* ubg, const pmpc_sqp_settings* ss, const pmpc_qp_settings* qs, double* x, double* lam,  \
-                                 pmpc_sqp_info* info) {                                                                               \
-            const std::vector<double> mp = ocp.model_params();                                                                        \
-            return pmpc_sqp_solve_batch(ctx, MODEL_ID, P, S, t0, tf, mp.empty() ? nullptr : mp.data(), (int)mp.size(), B, xg, lg, d,  \
-                                        lbx, ubx, lbg, ubg, ss, qs, x, lam, info);                                                    \
-        }                                                                                                                             \
-        static pmpc_status mpc_create(pmpc_context* ctx, const Name& ocp, int P, int S, double t0, double tf, int B, const double* d, \
-                                      const double* lbx, const double* ubx, const double* lbg, const double* ubg, const double* xg,   \
-                                      const double* lg, pmpc_mpc_batch** batch) {                                                     \
-            const std::vector<double> mp = ocp.model_params();                                                                        \
-            return pmpc_mpc_batch_create(ctx, MODEL_ID, P, S, t0, tf, mp.empty() ? nullptr : mp.data(), (int)mp.size(), B, d, lbx,    \
-                                         ubx, lbg, ubg, xg, lg, batch);                                                               \
-        }                                                                                                                             \
-    };
+// A model whose device code is inside libpolympc_amd.so, bound to the ABI by its model id; OCP::model_params() are its mparams (none: NULL, 0).
+template <class OCP, int MODEL_ID> struct builtin_device_binding {
+    static constexpr int model_id = MODEL_ID;   // what BatchSolver's prioritised solve asks for
+    static constexpr bool registered = false;
+    static pmpc_plant_dev_fn plant_fn() { return nullptr; }
+    static pmpc_status plant_step(pmpc_context* ctx, const OCP& ocp, int P, int S, double t0, double tf, int B, double dt, const pmpc_plant_settings* ps,
+                                  double* state, const double* u0, const double* iterate, const double* d, const double* w) {
+        const std::vector<double> mp = ocp.model_params();
+        return pmpc_plant_step_batch(ctx, MODEL_ID, mp.empty() ? nullptr : mp.data(), (int)mp.size(), P, S, t0, tf, B, dt, ps, state, u0, iterate, d, w);
+    }
+    static pmpc_status solve(pmpc_context* ctx, const OCP& ocp, int P, int S, double t0, double tf, int B, const double* xg, const double* lg,
+                             const double* d, const double* lbx, const double* ubx, const double* lbg, const double* ubg, const pmpc_sqp_settings* ss,
+                             const pmpc_qp_settings* qs, double* x, double* lam, pmpc_sqp_info* info) {
+        const std::vector<double> mp = ocp.model_params();
+        return pmpc_sqp_solve_batch(ctx, MODEL_ID, P, S, t0, tf, mp.empty() ? nullptr : mp.data(), (int)mp.size(), B, xg, lg, d, lbx, ubx, lbg, ubg, ss, qs,
+                                    x, lam, info);
+    }
+    static pmpc_status mpc_create(pmpc_context* ctx, const OCP& ocp, int P, int S, double t0, double tf, int B, const double* d, const double* lbx,
+                                  const double* ubx, const double* lbg, const double* ubg, const double* xg, const double* lg, pmpc_mpc_batch** batch) {
+        const std::vector<double> mp = ocp.model_params();
+        return pmpc_mpc_batch_create(ctx, MODEL_ID, P, S, t0, tf, mp.empty() ? nullptr : mp.data(), (int)mp.size(), B, d, lbx, ubx, lbg, ubg, xg, lg, batch);
+    }
+};
+#define POLYMPC_USE_BUILTIN_OCP(Name, MODEL_ID) \
+    template <> struct polympc::device_binding<Name> : polympc::builtin_device_binding<Name, MODEL_ID> {};
 
 // DeviceModel = the plain struct registered with PMPC_REGISTER_OCP in the .hip translation unit; the host OCP class exposes
 // `DeviceModel device_model() const` returning the parameter object that is copied into the kernel.
@@ -941,47 +938,8 @@ public:
     std::vector<double> model_params() const { return {}; }
 };
 }  // namespace models
-template <typename A> struct device_binding<models::MobileRobot<A>> {
-    static constexpr int model_id = PMPC_MODEL_ROBOT;   // built-in device code: what BatchSolver's prioritised solve asks for
-    static constexpr bool registered = false;
-    static pmpc_plant_dev_fn plant_fn() { return nullptr; }
-    static pmpc_status plant_step(pmpc_context* ctx, const models::MobileRobot<A>& ocp, int P, int S, double t0, double tf, int B, double dt, const pmpc_plant_settings* ps,
-                                  double* state, const double* u0, const double* iterate, const double* d, const double* w) {
-        const std::vector<double> mp = ocp.model_params();
-        return pmpc_plant_step_batch(ctx, PMPC_MODEL_ROBOT, mp.empty() ? nullptr : mp.data(), (int)mp.size(), P, S, t0, tf, B, dt, ps, state, u0, iterate, d, w);
-    }
-    static pmpc_status solve(pmpc_context* ctx, const models::MobileRobot<A>& ocp, int P, int S, double t0, double tf, int B, const double* xg,
-                             const double* lg, const double* d, const double* lbx, const double* ubx, const double* lbg, const double* ubg,
-                             const pmpc_sqp_settings* ss, const pmpc_qp_settings* qs, double* x, double* lam, pmpc_sqp_info* info) {
-        const std::vector<double> mp = ocp.model_params();
-        return pmpc_sqp_solve_batch(ctx, PMPC_MODEL_ROBOT, P, S, t0, tf, mp.data(), (int)mp.size(), B, xg, lg, d, lbx, ubx, lbg, ubg, ss, qs, x, lam, info);
-    }
-    static pmpc_status mpc_create(pmpc_context* ctx, const models::MobileRobot<A>& ocp, int P, int S, double t0, double tf, int B, const double* d,
-                                  const double* lbx, const double* ubx, const double* lbg, const double* ubg, const double* xg, const double* lg,
-                                  pmpc_mpc_batch** batch) {
-        const std::vector<double> mp = ocp.model_params();
-        return pmpc_mpc_batch_create(ctx, PMPC_MODEL_ROBOT, P, S, t0, tf, mp.data(), (int)mp.size(), B, d, lbx, ubx, lbg, ubg, xg, lg, batch);
-    }
-};
-template <typename A> struct device_binding<models::CSTR<A>> {
-    static constexpr int model_id = PMPC_MODEL_CSTR;
-    static constexpr bool registered = false;
-    static pmpc_plant_dev_fn plant_fn() { return nullptr; }
-    static pmpc_status plant_step(pmpc_context* ctx, const models::CSTR<A>& ocp, int P, int S, double t0, double tf, int B, double dt, const pmpc_plant_settings* ps,
-                                  double* state, const double* u0, const double* iterate, const double* d, const double* w) {
-        const std::vector<double> mp = ocp.model_params();
-        return pmpc_plant_step_batch(ctx, PMPC_MODEL_CSTR, mp.empty() ? nullptr : mp.data(), (int)mp.size(), P, S, t0, tf, B, dt, ps, state, u0, iterate, d, w);
-    }
-    static pmpc_status solve(pmpc_context* ctx, const models::CSTR<A>&, int P, int S, double t0, double tf, int B, const double* xg,
-                             const double* lg, const double* d, const double* lbx, const double* ubx, const double* lbg, const double* ubg,
-                             const pmpc_sqp_settings* ss, const pmpc_qp_settings* qs, double* x, double* lam, pmpc_sqp_info* info) {
-        return pmpc_sqp_solve_batch(ctx, PMPC_MODEL_CSTR, P, S, t0, tf, nullptr, 0, B, xg, lg, d, lbx, ubx, lbg, ubg, ss, qs, x, lam, info);
-    }
-    static pmpc_status mpc_create(pmpc_context* ctx, const models::CSTR<A>&, int P, int S, double t0, double tf, int B, const double* d, const double* lbx,
-                                  const double* ubx, const double* lbg, const double* ubg, const double* xg, const double* lg, pmpc_mpc_batch** batch) {
-        return pmpc_mpc_batch_create(ctx, PMPC_MODEL_CSTR, P, S, t0, tf, nullptr, 0, B, d, lbx, ubx, lbg, ubg, xg, lg, batch);
-    }
-};
+template <typename A> struct device_binding<models::MobileRobot<A>> : builtin_device_binding<models::MobileRobot<A>, PMPC_MODEL_ROBOT> {};
+template <typename A> struct device_binding<models::CSTR<A>> : builtin_device_binding<models::CSTR<A>, PMPC_MODEL_CSTR> {};
 }  // namespace polympc
 
 // ---------------------------------------------------------------------------------------------------------------------

@@ -23,26 +23,6 @@ ABI_VERSION = 4   # PMPC_ABI_VERSION of include/polympc_amd.h that the ctypes la
 ROUTE_NONE, ROUTE_REG1, ROUTE_REG2, ROUTE_LDS, ROUTE_HBM, ROUTE_SCHUR, ROUTE_CONDREG = 0, 1, 2, 3, 4, 5, 6   # pmpc_route
 ROUTE_NAMES = {0: "none", 1: "reg1", 2: "reg2", 3: "lds", 4: "hbm", 5: "schur", 6: "condreg"}
 
-EXPORTED_SYMBOLS = [
-    "pmpc_abi_version", "pmpc_struct_size", "pmpc_sqp_last_route",
-    "pmpc_version", "pmpc_status_string", "pmpc_create", "pmpc_destroy", "pmpc_synchronize", "pmpc_debug_phase_cycles", "pmpc_debug_set_poison",
-    "pmpc_qp_settings_default", "pmpc_qp_settings_sqp_default", "pmpc_sqp_settings_default", "pmpc_chebyshev",
-    "pmpc_qp_boxadmm_solve_batch", "pmpc_qp_boxadmm_solve_batch_dev", "pmpc_qp_boxadmm_solve_batch_f32", "pmpc_qp_boxadmm_solve_batch_f32_dev", "pmpc_qp_admm_solve_batch_f32", "pmpc_qp_admm_solve_batch_f32_dev", "pmpc_ocp_dims", "pmpc_ocp_linearise_batch",
-    "pmpc_sqp_solve_batch", "pmpc_sqp_solve_batch_dev", "pmpc_sqp_solve_batch_user", "pmpc_sqp_solve_batch_multi",
-    "pmpc_mpc_step_batch_user_dev", "pmpc_mpc_batch_create_user", "pmpc_mpc_batch_update",
-    "pmpc_mpc_step_batch_dev", "pmpc_mpc_batch_create", "pmpc_mpc_batch_step", "pmpc_mpc_batch_solution", "pmpc_mpc_batch_destroy",
-    "pmpc_dispatch_order_dev", "pmpc_sqp_work_priority_dev", "pmpc_sqp_solve_batch_prioritised", "pmpc_sqp_solve_batch_prioritised_dev",
-    "pmpc_mpc_step_batch_prioritised_dev", "pmpc_mpc_batch_set_dispatch",
-    "pmpc_traj_sample_batch", "pmpc_traj_sample_batch_dev", "pmpc_traj_shift_batch_dev", "pmpc_traj_regrid_batch", "pmpc_traj_regrid_batch_dev",
-    "pmpc_mpc_batch_sample", "pmpc_mpc_batch_shift",
-    "pmpc_plant_settings_default", "pmpc_plant_step_batch", "pmpc_plant_step_batch_dev", "pmpc_plant_step_batch_user", "pmpc_plant_step_batch_user_dev",
-    "pmpc_mpc_batch_set_plant", "pmpc_mpc_batch_rollout",
-    "pmpc_qp_admm_solve_batch", "pmpc_qp_admm_solve_batch_dev", "pmpc_qp_ruiz_compute_batch", "pmpc_qp_ruiz_compute_batch_dev", "pmpc_qp_ruiz_unscale_batch", "pmpc_qp_ruiz_unscale_batch_dev",
-    "pmpc_filter_state_create", "pmpc_filter_state_clear", "pmpc_filter_state_download", "pmpc_filter_state_destroy",
-    "pmpc_iteration_trace_create", "pmpc_iteration_trace_clear", "pmpc_iteration_trace_download", "pmpc_iteration_trace_destroy",
-    "pmpc_nlp_dims", "pmpc_nlp_linearise_batch", "pmpc_nlp_solve_batch", "pmpc_nlp_solve_batch_dev", "pmpc_nlp_solve_batch_user",
-]
-
 
 class QPSettings(C.Structure):
     _fields_ = [("eps_rel", C.c_double), ("eps_abs", C.c_double), ("max_iter", C.c_int), ("rho", C.c_double),
@@ -88,6 +68,124 @@ QP_INFO_DTYPE = np.dtype([("status", "i4"), ("iter", "i4"), ("rho_updates", "i4"
 SQP_INFO_DTYPE = np.dtype([("iter", "i4"), ("qp_solver_iter", "i4"), ("status", "i4"), ("flags", "i4"),
                            ("primal_norm", "f8"), ("dual_norm", "f8"), ("max_violation", "f8"), ("cost", "f8")])
 assert QP_INFO_DTYPE.itemsize == C.sizeof(QPInfo) == 40 and SQP_INFO_DTYPE.itemsize == C.sizeof(SQPInfo) == 48
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Every function include/polympc_amd.h declares, in the header's order: name -> (restype, argtypes). The one statement of the C signatures on the
+# Python side: lib() installs it on the loaded library, tests/test_capi_cpu.py compares all of it with the header. double* / float* and the
+# settings structs are typed pointers; opaque handles, function pointers, info arrays, int arrays and device handles are c_void_p; a T** that
+# receives a handle is POINTER(c_void_p).
+_I, _D, _V = C.c_int, C.c_double, C.c_void_p
+_P, _F, _H = C.POINTER(C.c_double), C.POINTER(C.c_float), C.POINTER(C.c_void_p)
+_QS, _SS, _PS = C.POINTER(QPSettings), C.POINTER(SQPSettings), C.POINTER(PlantSettings)
+_QP_HEAD = [_V, _I, _I, _I]                       # ctx, B, n, m
+_OCP_GRID = [_I, _I, _I, _D, _D, _P, _I]          # model, P, S, t0, tf, mparams, n_mparams
+_SQP_IN = [_P] * 7                                # x_guess, lam_guess, d, lbx, ubx, lbg, ubg
+_MPC_IN = [_P] * 6                                # x0, d, lbx, ubx, lbg, ubg
+_SQP_TAIL = [_SS, _QS, _P, _P, _V]                # sqp_settings, qp_settings, x, lam, info
+_USER_OCP_HEAD = [_V, _V, _V]                     # ctx, fn, model
+_USER_OCP_GRID = [_I] * 7 + [_D] * 2              # nx, nu, np, nd, ng, P, S, t0, tf
+_TRAJ_HEAD = [_V, _I, _I, _I, _I]                 # ctx, B, nx, nu, np
+_PLANT_TAIL = [_I, _D, _PS] + [_P] * 5            # B, dt, settings, state, u0, iterate, d, w
+
+
+def _qp(T):
+    """a QP solve on arrays of T: H, h, A, Alb, Aub, xlb, xub, x0, y0, settings, x, y, info"""
+    return _I, _QP_HEAD + [T] * 9 + [_QS, T, T, _V]
+
+
+_SQP = _I, [_V] + _OCP_GRID + [_I] + _SQP_IN + _SQP_TAIL                  # pmpc_sqp_solve_batch and its _dev twin
+_MPC_STEP = [_V] + _OCP_GRID + [_I] + _MPC_IN + _SQP_TAIL + [_P]         # pmpc_mpc_step_batch_dev: ..., u0
+_NLP = _I, [_V, _I, _I] + _SQP_IN + _SQP_TAIL                             # ctx, problem, B, ...
+_TRAJ_SAMPLE = _I, _TRAJ_HEAD + [_I, _I, _D, _D, _P, _I, _P, _I, _P, _P]  # P, S, t0, tf, x, K, t, t_per_instance, xs, us
+_TRAJ_REGRID = _I, _TRAJ_HEAD + [_I] * 4 + [_D, _D, _P, _P]               # P, S, P2, S2, t0, tf, x_src, x_dst
+_PLANT = _I, [_V, _I, _P, _I, _I, _I, _D, _D] + _PLANT_TAIL               # ctx, model, mparams, n_mparams, P, S, t0, tf, ...
+_PLANT_USER = _I, _USER_OCP_HEAD + [_I] * 6 + [_D, _D] + _PLANT_TAIL      # ctx, fn, model, nx, nu, np, nd, P, S, t0, tf, ...
+
+SIGNATURES = {
+    # ---- version, context, defaults
+    "pmpc_abi_version": (_I, []),
+    "pmpc_struct_size": (C.c_ulong, [_I]),
+    "pmpc_version": (C.c_char_p, []),
+    "pmpc_status_string": (C.c_char_p, [_I]),
+    "pmpc_create": (_I, [_I, _V, _H]),
+    "pmpc_destroy": (_I, [_V]),
+    "pmpc_synchronize": (_I, [_V]),
+    "pmpc_debug_phase_cycles": (_I, [_V, _V, _I]),
+    "pmpc_debug_set_poison": (_I, [_V, _I]),
+    "pmpc_sqp_last_route": (_I, [_V]),
+    "pmpc_qp_settings_default": (None, [_QS]),
+    "pmpc_qp_settings_sqp_default": (None, [_QS]),
+    "pmpc_sqp_settings_default": (None, [_SS]),
+    "pmpc_chebyshev": (_I, [_I, _P, _P, _P]),
+    # ---- QPs
+    "pmpc_qp_boxadmm_solve_batch": _qp(_P),
+    "pmpc_qp_boxadmm_solve_batch_dev": _qp(_P),
+    "pmpc_qp_boxadmm_solve_batch_f32": _qp(_F),
+    "pmpc_qp_boxadmm_solve_batch_f32_dev": _qp(_F),
+    "pmpc_qp_admm_solve_batch_f32": _qp(_F),
+    "pmpc_qp_admm_solve_batch_f32_dev": _qp(_F),
+    "pmpc_qp_admm_solve_batch": _qp(_P),
+    "pmpc_qp_admm_solve_batch_dev": _qp(_P),
+    "pmpc_qp_ruiz_compute_batch": (_I, _QP_HEAD + [_P] * 10),
+    "pmpc_qp_ruiz_compute_batch_dev": (_I, _QP_HEAD + [_P] * 10),
+    "pmpc_qp_ruiz_unscale_batch": (_I, _QP_HEAD + [_P] * 5),
+    "pmpc_qp_ruiz_unscale_batch_dev": (_I, _QP_HEAD + [_P] * 5),
+    # ---- built-in OCPs: dimensions, linearisation, SQP solves, filter and trace handles
+    "pmpc_ocp_dims": (_I, [_I, _I, _I] + [_V] * 8),
+    "pmpc_ocp_linearise_batch": (_I, [_V] + _OCP_GRID + [_I] + [_P] * 9),
+    "pmpc_sqp_solve_batch": _SQP,
+    "pmpc_sqp_solve_batch_multi": (_I, [_H, _I] + _OCP_GRID + [_I] + _SQP_IN + _SQP_TAIL),
+    "pmpc_sqp_solve_batch_dev": _SQP,
+    "pmpc_filter_state_create": (_I, [_V, _I, _H]),
+    "pmpc_filter_state_clear": (_I, [_V, _I, _V]),
+    "pmpc_filter_state_download": (_I, [_V, _I, _V, _P]),
+    "pmpc_filter_state_destroy": (_I, [_V, _V]),
+    "pmpc_iteration_trace_create": (_I, [_V, _I, _I, _H]),
+    "pmpc_iteration_trace_clear": (_I, [_V, _I, _I, _V]),
+    "pmpc_iteration_trace_download": (_I, [_V, _I, _I, _V, _P]),
+    "pmpc_iteration_trace_destroy": (_I, [_V, _V]),
+    # ---- MPC step and the opaque batch
+    "pmpc_mpc_step_batch_dev": (_I, _MPC_STEP),
+    "pmpc_mpc_batch_create": (_I, [_V] + _OCP_GRID + [_I] + [_P] * 7 + [_H]),
+    "pmpc_mpc_batch_step": (_I, [_V, _P, _SS, _QS, _P, _V]),
+    "pmpc_mpc_batch_solution": (_I, [_V, _P, _P]),
+    "pmpc_mpc_batch_destroy": (_I, [_V]),
+    # ---- longest-first dispatch
+    "pmpc_dispatch_order_dev": (_I, [_V, _I, _V, _V]),
+    "pmpc_sqp_work_priority_dev": (_I, [_V, _I, _V, _I, _V]),
+    "pmpc_sqp_solve_batch_prioritised_dev": (_I, _SQP[1] + [_V]),
+    "pmpc_sqp_solve_batch_prioritised": (_I, _SQP[1] + [_V]),
+    "pmpc_mpc_step_batch_prioritised_dev": (_I, _MPC_STEP + [_V, _I]),
+    "pmpc_mpc_batch_set_dispatch": (_I, [_V, _I, _I]),
+    # ---- trajectories
+    "pmpc_traj_sample_batch_dev": _TRAJ_SAMPLE,
+    "pmpc_traj_sample_batch": _TRAJ_SAMPLE,
+    "pmpc_traj_shift_batch_dev": (_I, _TRAJ_HEAD + [_I, _I, _I, _D, _D, _D, _P, _P]),   # ng, P, S, t0, tf, dt, x, lam
+    "pmpc_traj_regrid_batch_dev": _TRAJ_REGRID,
+    "pmpc_traj_regrid_batch": _TRAJ_REGRID,
+    "pmpc_mpc_batch_sample": (_I, [_V, _I, _P, _I, _P, _P]),
+    "pmpc_mpc_batch_shift": (_I, [_V, _D, _I]),
+    # ---- user-defined OCPs
+    "pmpc_sqp_solve_batch_user": (_I, _USER_OCP_HEAD + _USER_OCP_GRID + [_I] + _SQP_IN + _SQP_TAIL),
+    "pmpc_mpc_step_batch_user_dev": (_I, _USER_OCP_HEAD + _USER_OCP_GRID + [_I] + _MPC_IN + _SQP_TAIL + [_P, _V, _I]),   # ..., u0, priority, iter_weight
+    "pmpc_mpc_batch_create_user": (_I, _USER_OCP_HEAD + [C.c_ulong] + _USER_OCP_GRID + [_I] + [_P] * 7 + [_H]),
+    "pmpc_mpc_batch_update": (_I, [_V] + [_P] * 5),
+    # ---- the plant of a closed loop
+    "pmpc_plant_settings_default": (None, [_PS]),
+    "pmpc_plant_step_batch_dev": _PLANT,
+    "pmpc_plant_step_batch": _PLANT,
+    "pmpc_plant_step_batch_user_dev": _PLANT_USER,
+    "pmpc_plant_step_batch_user": _PLANT_USER,
+    "pmpc_mpc_batch_set_plant": (_I, [_V, _PS, _P, _V]),
+    "pmpc_mpc_batch_rollout": (_I, [_V, _P, _I, _D, _I, _SS, _QS, _P, _P, _P, _V]),
+    # ---- generic NLPs
+    "pmpc_nlp_dims": (_I, [_I] + [_V] * 4),
+    "pmpc_nlp_linearise_batch": (_I, [_V, _I, _I] + [_P] * 9),
+    "pmpc_nlp_solve_batch": _NLP,
+    "pmpc_nlp_solve_batch_dev": _NLP,
+    "pmpc_nlp_solve_batch_user": (_I, [_V, _V, _V] + [_I] * 5 + _SQP_IN + _SQP_TAIL),   # ctx, fn, model, nx, ne, ni, np, B, ...
+}
+EXPORTED_SYMBOLS = list(SIGNATURES)
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC"]
 BUILD_DIR = os.path.join(HERE, "_build")
@@ -136,8 +234,6 @@ def lib():
                 f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`. "
                 "polympc_amd has no CPU fallback.")
         L = C.CDLL(LIB_PATH)
-        L.pmpc_version.restype = C.c_char_p
-        L.pmpc_status_string.restype = C.c_char_p
         # a stale library next to new ctypes layouts (or the reverse) would have pmpc_*_settings_default() write past a struct, or hand the
         # kernels garbage in the fields it does not know: refuse it here
         if not hasattr(L, "pmpc_abi_version"):
@@ -149,6 +245,10 @@ def lib():
         if (got != ABI_VERSION and not os.environ.get("PMPC_ABI_ANY")) or sizes != want:   # PMPC_ABI_ANY: developer switch for timing an older build (PMPC_LIB) whose struct sizes agree
             raise RuntimeError(f"{LIB_PATH}: ABI version {got} / struct sizes {sizes}, this binding expects version {ABI_VERSION} / {want}: "
                                "rebuild the library from the same tree")
+        for name, (restype, argtypes) in SIGNATURES.items():   # a same-ABI library may predate the newer entry points: those fail at their first use
+            if hasattr(L, name):
+                f = getattr(L, name)
+                f.restype, f.argtypes = restype, argtypes
         _lib = L
     return _lib
 
@@ -214,10 +314,6 @@ def nlp_dims(problem):
     return dict(nx=nx, ne=ne, ni=ni, np=np_, m=ne + ni)
 
 
-_NLP_SOLVE_ARGTYPES = [C.POINTER(C.c_double)] * 7 + [C.POINTER(SQPSettings), C.POINTER(QPSettings), C.POINTER(C.c_double),
-                                                     C.POINTER(C.c_double), C.c_void_p]
-
-
 def _nlp_host_call(f, lead, B, dims, x_guess, lam_guess, d, lbx, ubx, lbg, ubg, sqp_settings, qp_settings):
     """the host-buffer NLP solves: shared staging of the optional inputs and the outputs"""
     nx, m = dims["nx"], dims["m"]
@@ -246,15 +342,9 @@ class UserNLP:
 
     def solve_batch(self, ctx, B, x_guess=None, lam_guess=None, d=None, lbx=None, ubx=None, lbg=None, ubg=None, sqp_settings=None,
                     qp_settings=None):
-        f = lib().pmpc_nlp_solve_batch_user
-        f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 5 + _NLP_SOLVE_ARGTYPES
         dm = self.dims
         lead = (ctx._ctx, C.cast(self.fn, C.c_void_p), C.cast(self.model, C.c_void_p), dm["nx"], dm["ne"], dm["ni"], dm["np"])
-        return _nlp_host_call(f, lead, B, dm, x_guess, lam_guess, d, lbx, ubx, lbg, ubg, sqp_settings, qp_settings)
-
-
-_USER_OCP_HEAD = [C.c_void_p, C.c_void_p, C.c_void_p]   # ctx, fn, model
-_USER_OCP_GRID = [C.c_int] * 7 + [C.c_double] * 2       # nx, nu, np, nd, ng, P, S, t0, tf
+        return _nlp_host_call(lib().pmpc_nlp_solve_batch_user, lead, B, dm, x_guess, lam_guess, d, lbx, ubx, lbg, ubg, sqp_settings, qp_settings)
 
 
 class UserOCP:
@@ -295,9 +385,7 @@ class UserOCP:
         x = np.zeros((B, n)); lam = np.zeros((B, m + n)); info = np.zeros(B, dtype=SQP_INFO_DTYPE)
         keep = [_h(a) for a in (x_guess, lam_guess, d, lbx, ubx, lbg, ubg)]
         P_ = C.POINTER(C.c_double)
-        f = lib().pmpc_sqp_solve_batch_user
-        f.argtypes = _USER_OCP_HEAD + _USER_OCP_GRID + [C.c_int] + [P_] * 7 + [C.POINTER(SQPSettings), C.POINTER(QPSettings), P_, P_, C.c_void_p]
-        _check_status(f(*self._head(ctx), *self._grid(P, S, t0, tf), int(B), *[k[1] for k in keep], C.byref(ss), C.byref(qs), x.ctypes.data_as(P_),
+        _check_status(lib().pmpc_sqp_solve_batch_user(*self._head(ctx), *self._grid(P, S, t0, tf), int(B), *[k[1] for k in keep], C.byref(ss), C.byref(qs), x.ctypes.data_as(P_),
                         lam.ctypes.data_as(P_), C.c_void_p(info.ctypes.data)))
         return x, lam, info
 
@@ -305,12 +393,9 @@ class UserOCP:
                            priority=None, iter_weight=0):
         """pmpc_mpc_step_batch_user_dev on torch CUDA tensors; priority: None (index order) or an int32 tensor, read as this step's priorities and
         overwritten with iter_weight * iter + qp_solver_iter of this step's solve. Asynchronous on the context's stream."""
-        P_ = C.POINTER(C.c_double)
-        f = lib().pmpc_mpc_step_batch_user_dev
-        f.argtypes = _USER_OCP_HEAD + _USER_OCP_GRID + [C.c_int] + [P_] * 6 + [C.POINTER(SQPSettings), C.POINTER(QPSettings), P_, P_, C.c_void_p, P_,
-                                                                                C.c_void_p, C.c_int]
-        _check_status(f(*self._head(ctx), *self._grid(P, S, t0, tf), int(B), _d(x0), _d(d), _d(lbx), _d(ubx), _d(lbg), _d(ubg), C.byref(sqp_settings),
-                        C.byref(qp_settings), _d(x), _d(lam), C.c_void_p(info.data_ptr()), _d(u0), _dv(priority), int(iter_weight)))
+        _check_status(lib().pmpc_mpc_step_batch_user_dev(*self._head(ctx), *self._grid(P, S, t0, tf), int(B), _d(x0), _d(d), _d(lbx), _d(ubx), _d(lbg),
+                                                         _d(ubg), C.byref(sqp_settings), C.byref(qp_settings), _d(x), _d(lam),
+                                                         C.c_void_p(info.data_ptr()), _d(u0), _dv(priority), int(iter_weight)))
 
     @property
     def plant_fn(self):
@@ -324,7 +409,6 @@ class UserOCP:
         return self._plant_fn
 
     def _plant_call(self, f, ctx, P, S, t0, tf, B, dt, settings, ptrs):
-        f.argtypes = _USER_OCP_HEAD + [C.c_int] * 6 + [C.c_double] * 2 + [C.c_int, C.c_double, C.POINTER(PlantSettings)] + [C.POINTER(C.c_double)] * 5
         _check_status(f(ctx._ctx, C.cast(self.plant_fn, C.c_void_p), C.cast(self.model, C.c_void_p), self.nx, self.nu, self.np, self.nd, int(P), int(S),
                         float(t0), float(tf), int(B), float(dt), C.byref(settings or plant_settings_default()), *ptrs))
 
@@ -377,20 +461,16 @@ class MPCBatch:
         self.B = int(B)
         self._batch = C.c_void_p()
         self._user = model if isinstance(model, UserOCP) else None
-        P_ = C.POINTER(C.c_double)
         if isinstance(model, UserOCP):
             self.dims = model.dims(P, S)
             keep = [_h(a) for a in (d, lbx, ubx, lbg, ubg, x_guess, lam_guess)]
-            f = lib().pmpc_mpc_batch_create_user
-            f.argtypes = _USER_OCP_HEAD + [C.c_ulong] + _USER_OCP_GRID + [C.c_int] + [P_] * 7 + [C.POINTER(C.c_void_p)]
-            _check_status(f(*model._head(ctx), model.model_bytes, *model._grid(P, S, t0, tf), self.B, *[k[1] for k in keep], C.byref(self._batch)))
+            _check_status(lib().pmpc_mpc_batch_create_user(*model._head(ctx), model.model_bytes, *model._grid(P, S, t0, tf), self.B,
+                                                           *[k[1] for k in keep], C.byref(self._batch)))
             return
         self.dims = ocp_dims(model, P, S)
         keep = [_h(a) for a in (mparams, d, lbx, ubx, lbg, ubg, x_guess, lam_guess)]
-        f = lib().pmpc_mpc_batch_create
-        f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, P_, C.c_int, C.c_int] + [P_] * 7 + [C.POINTER(C.c_void_p)]
-        _check_status(f(ctx._ctx, model, P, S, t0, tf, keep[0][1], 0 if keep[0][0] is None else len(keep[0][0]), self.B, *[k[1] for k in keep[1:]],
-                        C.byref(self._batch)))
+        _check_status(lib().pmpc_mpc_batch_create(ctx._ctx, model, P, S, t0, tf, keep[0][1], 0 if keep[0][0] is None else len(keep[0][0]), self.B,
+                                                  *[k[1] for k in keep[1:]], C.byref(self._batch)))
 
     def update(self, d=None, lbx=None, ubx=None, lbg=None, ubg=None):
         """pmpc_mpc_batch_update: new static parameters / bounds (host arrays of the sizes given at creation; None keeps what the batch holds)"""
@@ -398,24 +478,19 @@ class MPCBatch:
         dm = self.dims
         for (a, _), per in zip(keep, (dm["nd"], dm["n"], dm["n"], dm["m_ineq"], dm["m_ineq"])):
             assert a is None or a.size == self.B * per, "an array of another size than at creation"
-        f = lib().pmpc_mpc_batch_update
-        f.argtypes = [C.c_void_p] + [C.POINTER(C.c_double)] * 5
-        _check_status(f(self._batch, *[k[1] for k in keep]))
+        _check_status(lib().pmpc_mpc_batch_update(self._batch, *[k[1] for k in keep]))
 
     def set_dispatch(self, mode, iter_weight=0):
         """pmpc_mpc_batch_set_dispatch: 0 index order (default), 1 longest first by the previous step's counts"""
-        f = lib().pmpc_mpc_batch_set_dispatch
-        f.argtypes = [C.c_void_p, C.c_int, C.c_int]
-        _check_status(f(self._batch, int(mode), int(iter_weight)))
+        _check_status(lib().pmpc_mpc_batch_set_dispatch(self._batch, int(mode), int(iter_weight)))
 
     def step(self, x0, sqp_settings, qp_settings):
         """pmpc_mpc_batch_step -> u0 (B, nu), info"""
         xk, xp = _h(x0)
         u0 = np.zeros((self.B, self.dims["nu"])); info = np.zeros(self.B, dtype=SQP_INFO_DTYPE)
         P_ = C.POINTER(C.c_double)
-        f = lib().pmpc_mpc_batch_step
-        f.argtypes = [C.c_void_p, P_, C.POINTER(SQPSettings), C.POINTER(QPSettings), P_, C.c_void_p]
-        _check_status(f(self._batch, xp, C.byref(sqp_settings), C.byref(qp_settings), u0.ctypes.data_as(P_), C.c_void_p(info.ctypes.data)))
+        _check_status(lib().pmpc_mpc_batch_step(self._batch, xp, C.byref(sqp_settings), C.byref(qp_settings), u0.ctypes.data_as(P_),
+                                                C.c_void_p(info.ctypes.data)))
         return u0, info
 
     def solution(self):
@@ -423,9 +498,7 @@ class MPCBatch:
         n, m = self.dims["n"], self.dims["m"]
         x = np.zeros((self.B, n)); lam = np.zeros((self.B, m + n))
         P_ = C.POINTER(C.c_double)
-        f = lib().pmpc_mpc_batch_solution
-        f.argtypes = [C.c_void_p, P_, P_]
-        _check_status(f(self._batch, x.ctypes.data_as(P_), lam.ctypes.data_as(P_)))
+        _check_status(lib().pmpc_mpc_batch_solution(self._batch, x.ctypes.data_as(P_), lam.ctypes.data_as(P_)))
         return x, lam
 
     def sample(self, t, per_instance=False, want_x=True, want_u=True):
@@ -436,27 +509,20 @@ class MPCBatch:
         assert tk.size == (self.B * K if per_instance else K)
         xs = np.zeros((self.B, K, self.dims["nx"])) if want_x else None
         us = np.zeros((self.B, K, self.dims["nu"])) if want_u else None
-        P_ = C.POINTER(C.c_double)
-        f = lib().pmpc_mpc_batch_sample
-        f.argtypes = [C.c_void_p, C.c_int, P_, C.c_int, P_, P_]
-        _check_status(f(self._batch, int(K), tp, 1 if per_instance else 0, _h(xs)[1], _h(us)[1]))
+        _check_status(lib().pmpc_mpc_batch_sample(self._batch, int(K), tp, 1 if per_instance else 0, _h(xs)[1], _h(us)[1]))
         return xs, us
 
     def shift(self, dt, duals=False):
         """pmpc_mpc_batch_shift: move the batch's iterate (duals: and its multipliers) forward by dt; the next step starts from it"""
-        f = lib().pmpc_mpc_batch_shift
-        f.argtypes = [C.c_void_p, C.c_double, C.c_int]
-        _check_status(f(self._batch, float(dt), 1 if duals else 0))
+        _check_status(lib().pmpc_mpc_batch_shift(self._batch, float(dt), 1 if duals else 0))
 
     def set_plant(self, settings=None, d_plant=None):
         """pmpc_mpc_batch_set_plant: the plant of rollout() — settings (default: RK4, 1 substep, zero-order hold) and the plant's own static
         parameters (B, nd), None = the controller's; a registered OCP's batch passes its pmpc_user_plant_dev_<name>"""
         dk, dp = _h(d_plant)
         assert dk is None or dk.size == self.B * self.dims["nd"], "d_plant of another size than the batch's static parameters"
-        f = lib().pmpc_mpc_batch_set_plant
-        f.argtypes = [C.c_void_p, C.POINTER(PlantSettings), C.POINTER(C.c_double), C.c_void_p]
-        _check_status(f(self._batch, C.byref(settings or plant_settings_default()), dp,
-                        C.cast(self._user.plant_fn, C.c_void_p) if self._user is not None else None))
+        _check_status(lib().pmpc_mpc_batch_set_plant(self._batch, C.byref(settings or plant_settings_default()), dp,
+                                                     C.cast(self._user.plant_fn, C.c_void_p) if self._user is not None else None))
 
     def rollout(self, x0, K, dt, sqp_settings, qp_settings, shift=0, w=None):
         """pmpc_mpc_batch_rollout: K closed-loop steps on the device from the states x0 (B, nx); shift 0 none / 1 the primal warm start / 2 the duals
@@ -467,10 +533,8 @@ class MPCBatch:
         xs = np.zeros((self.B, max(K, 0) + 1, self.dims["nx"])); us = np.zeros((self.B, max(K, 0), self.dims["nu"]))
         info = np.zeros((self.B, max(K, 0)), dtype=SQP_INFO_DTYPE)
         P_ = C.POINTER(C.c_double)
-        f = lib().pmpc_mpc_batch_rollout
-        f.argtypes = [C.c_void_p, P_, C.c_int, C.c_double, C.c_int, C.POINTER(SQPSettings), C.POINTER(QPSettings), P_, P_, P_, C.c_void_p]
-        _check_status(f(self._batch, xp, K, float(dt), int(shift), C.byref(sqp_settings), C.byref(qp_settings), wp, xs.ctypes.data_as(P_),
-                        us.ctypes.data_as(P_), C.c_void_p(info.ctypes.data)))
+        _check_status(lib().pmpc_mpc_batch_rollout(self._batch, xp, K, float(dt), int(shift), C.byref(sqp_settings), C.byref(qp_settings), wp,
+                                                   xs.ctypes.data_as(P_), us.ctypes.data_as(P_), C.c_void_p(info.ctypes.data)))
         return xs, us, info
 
     def close(self):
@@ -485,11 +549,14 @@ class Context:
     def __init__(self, device=0, stream=None):
         self._ctx = C.c_void_p()
         _check(lib().pmpc_create(int(device), C.c_void_p(stream) if stream else None, C.byref(self._ctx)))
+        self._created = True
 
     def close(self):
-        if self._ctx:
+        # only a handle pmpc_create gave this object is destroyed: one made with __new__ around another pointer (the wrapper-driving CPU tests)
+        # must not take the process down when it is collected after a failed assertion
+        if self._ctx and getattr(self, "_created", False):
             lib().pmpc_destroy(self._ctx)
-            self._ctx = C.c_void_p()
+        self._ctx = C.c_void_p()
 
     def __del__(self):
         try:
@@ -542,7 +609,6 @@ class Context:
         s = settings or qp_settings_default()
         x = np.zeros((B, n), dtype=np.float32); y = np.zeros((B, n + m), dtype=np.float32); info = np.zeros(B, dtype=QP_INFO_DTYPE)
         f = lib().pmpc_qp_admm_solve_batch_f32 if osqp_form else lib().pmpc_qp_boxadmm_solve_batch_f32
-        f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.POINTER(C.c_float)] * 9 + [C.POINTER(QPSettings)] + [C.POINTER(C.c_float)] * 2 + [C.c_void_p]
         _check(f(self._ctx, B, n, m, pf(H), pf(h), pf(A), pf(Alb), pf(Aub), pf(xlb), pf(xub), pf(x0), pf(y0), C.byref(s), pf(x), pf(y),
                  C.c_void_p(info.ctypes.data)))
         return x, y, info
@@ -579,10 +645,8 @@ class Context:
         cost = np.zeros((B, 2)); c = np.zeros((B, m)); jac = np.zeros((B, m * n)); cg = np.zeros((B, n)); lg = np.zeros((B, n))
         lh = np.zeros((B, n * n))
         P_ = C.POINTER(C.c_double)
-        f = lib().pmpc_ocp_linearise_batch
-        f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, P_, C.c_int, C.c_int] + [P_] * 9
-        _check(f(self._ctx, model, P, S, t0, tf, mp, 0 if mk is None else len(mk), B, vp, dp_, lp,
-                 *[a.ctypes.data_as(P_) for a in (cost, c, jac, cg, lg, lh)]))
+        _check(lib().pmpc_ocp_linearise_batch(self._ctx, model, P, S, t0, tf, mp, 0 if mk is None else len(mk), B, vp, dp_, lp,
+                                              *[a.ctypes.data_as(P_) for a in (cost, c, jac, cg, lg, lh)]))
         return dict(cost=cost[:, 0], cost_values_only=cost[:, 1], c=c, jac=jac.reshape(B, n, m).transpose(0, 2, 1).copy(),
                     cost_grad=cg, lag_grad=lg, lag_hess=lh.reshape(B, n, n).transpose(0, 2, 1).copy())
 
@@ -594,12 +658,9 @@ class Context:
         x = np.zeros((B, n)); lam = np.zeros((B, m + n)); info = np.zeros(B, dtype=SQP_INFO_DTYPE)
         keep = [_h(a) for a in (mparams, x_guess, lam_guess, d, lbx, ubx, lbg, ubg)]
         P_ = C.POINTER(C.c_double)
-        f = lib().pmpc_sqp_solve_batch
-        f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, P_, C.c_int, C.c_int] + [P_] * 7 + \
-                     [C.POINTER(SQPSettings), C.POINTER(QPSettings), P_, P_, C.c_void_p]
-        _check(f(self._ctx, model, P, S, t0, tf, keep[0][1], 0 if keep[0][0] is None else len(keep[0][0]), B,
-                 *[k[1] for k in keep[1:]], C.byref(ss), C.byref(qs), x.ctypes.data_as(P_), lam.ctypes.data_as(P_),
-                 C.c_void_p(info.ctypes.data)))
+        _check(lib().pmpc_sqp_solve_batch(self._ctx, model, P, S, t0, tf, keep[0][1], 0 if keep[0][0] is None else len(keep[0][0]), B,
+                                          *[k[1] for k in keep[1:]], C.byref(ss), C.byref(qs), x.ctypes.data_as(P_), lam.ctypes.data_as(P_),
+                                          C.c_void_p(info.ctypes.data)))
         return x, lam, info
 
     @staticmethod
@@ -612,89 +673,63 @@ class Context:
         keep = [_h(a) for a in (mparams, x_guess, lam_guess, d, lbx, ubx, lbg, ubg)]
         P_ = C.POINTER(C.c_double)
         arr = (C.c_void_p * len(ctxs))(*[c._ctx for c in ctxs])
-        f = lib().pmpc_sqp_solve_batch_multi
-        f.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, P_, C.c_int, C.c_int] + [P_] * 7 + \
-                     [C.POINTER(SQPSettings), C.POINTER(QPSettings), P_, P_, C.c_void_p]
-        _check(f(arr, len(ctxs), model, P, S, t0, tf, keep[0][1], 0 if keep[0][0] is None else len(keep[0][0]), B,
-                 *[k[1] for k in keep[1:]], C.byref(ss), C.byref(qs), x.ctypes.data_as(P_), lam.ctypes.data_as(P_),
-                 C.c_void_p(info.ctypes.data)))
+        _check(lib().pmpc_sqp_solve_batch_multi(arr, len(ctxs), model, P, S, t0, tf, keep[0][1], 0 if keep[0][0] is None else len(keep[0][0]), B,
+                                                *[k[1] for k in keep[1:]], C.byref(ss), C.byref(qs), x.ctypes.data_as(P_), lam.ctypes.data_as(P_),
+                                                C.c_void_p(info.ctypes.data)))
         return x, lam, info
 
     # ------------------------------------------------------------------ LSFilter state of B solver objects (line_search = 1)
     def filter_state_create(self, B):
         """Device buffer of B empty filters; put the returned handle into SQPSettings.filter_state to carry the filter between solves."""
         out = C.c_void_p()
-        f = lib().pmpc_filter_state_create
-        f.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
-        _check(f(self._ctx, B, C.byref(out)))
+        _check(lib().pmpc_filter_state_create(self._ctx, B, C.byref(out)))
         return out.value
 
     def filter_state_clear(self, B, handle):
-        f = lib().pmpc_filter_state_clear
-        f.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-        _check(f(self._ctx, B, handle))
+        _check(lib().pmpc_filter_state_clear(self._ctx, B, handle))
 
     def filter_state_download(self, B, handle):
         out = np.zeros((B, FILTER_STATE_DOUBLES))
-        f = lib().pmpc_filter_state_download
-        f.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_double)]
-        _check(f(self._ctx, B, handle, out.ctypes.data_as(C.POINTER(C.c_double))))
+        _check(lib().pmpc_filter_state_download(self._ctx, B, handle, out.ctypes.data_as(C.POINTER(C.c_double))))
         return out
 
     def filter_state_destroy(self, handle):
-        f = lib().pmpc_filter_state_destroy
-        f.argtypes = [C.c_void_p, C.c_void_p]
-        _check(f(self._ctx, handle))
+        _check(lib().pmpc_filter_state_destroy(self._ctx, handle))
 
     # ------------------------------------------------------------------ per-iteration records (the reference's iteration_callback, recorded)
     def iteration_trace_create(self, B, capacity):
         """Device buffer of B x capacity zeroed records; put the handle into SQPSettings.iteration_trace (and the capacity next to it)."""
         out = C.c_void_p()
-        f = lib().pmpc_iteration_trace_create
-        f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
-        _check(f(self._ctx, B, capacity, C.byref(out)))
+        _check(lib().pmpc_iteration_trace_create(self._ctx, B, capacity, C.byref(out)))
         return out.value
 
     def iteration_trace_clear(self, B, capacity, handle):
-        f = lib().pmpc_iteration_trace_clear
-        f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
-        _check(f(self._ctx, B, capacity, handle))
+        _check(lib().pmpc_iteration_trace_clear(self._ctx, B, capacity, handle))
 
     def iteration_trace_download(self, B, capacity, handle):
         out = np.zeros((B, capacity, TRACE_DOUBLES))
-        f = lib().pmpc_iteration_trace_download
-        f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_double)]
-        _check(f(self._ctx, B, capacity, handle, out.ctypes.data_as(C.POINTER(C.c_double))))
+        _check(lib().pmpc_iteration_trace_download(self._ctx, B, capacity, handle, out.ctypes.data_as(C.POINTER(C.c_double))))
         return out
 
     def iteration_trace_destroy(self, handle):
-        f = lib().pmpc_iteration_trace_destroy
-        f.argtypes = [C.c_void_p, C.c_void_p]
-        _check(f(self._ctx, handle))
+        _check(lib().pmpc_iteration_trace_destroy(self._ctx, handle))
 
     # ------------------------------------------------------------------ MPC step, device buffers (torch tensors), asynchronous
     def mpc_step_batch_dev(self, model, P, S, t0, tf, B, x0, d, lbx, ubx, x, lam, info, sqp_settings, qp_settings, u0=None, lbg=None,
                            ubg=None, mparams=None):
         mk, mp = _h(mparams)
-        P_ = C.POINTER(C.c_double)
-        f = lib().pmpc_mpc_step_batch_dev
-        f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, P_, C.c_int, C.c_int] + [P_] * 6 + \
-                     [C.POINTER(SQPSettings), C.POINTER(QPSettings), P_, P_, C.c_void_p, P_]
-        _check(f(self._ctx, model, P, S, t0, tf, mp, 0 if mk is None else len(mk), B, _d(x0), _d(d), _d(lbx), _d(ubx), _d(lbg), _d(ubg),
-                 C.byref(sqp_settings), C.byref(qp_settings), _d(x), _d(lam), C.c_void_p(info.data_ptr()), _d(u0)))
+        _check(lib().pmpc_mpc_step_batch_dev(self._ctx, model, P, S, t0, tf, mp, 0 if mk is None else len(mk), B, _d(x0), _d(d), _d(lbx), _d(ubx),
+                                             _d(lbg), _d(ubg), C.byref(sqp_settings), C.byref(qp_settings), _d(x), _d(lam),
+                                             C.c_void_p(info.data_ptr()), _d(u0)))
 
     # ------------------------------------------------------------------ longest-first dispatch (pmpc_dispatch_order_dev and the prioritised solves)
     def dispatch_order_dev(self, B, priority, order):
         """pmpc_dispatch_order_dev on torch int32 CUDA tensors (priority may be None: identity); asynchronous on the context's stream"""
-        f = lib().pmpc_dispatch_order_dev
-        f.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-        _check_status(f(self._ctx, int(B), _dv(priority), _dv(order)))
+        _check_status(lib().pmpc_dispatch_order_dev(self._ctx, int(B), _dv(priority), _dv(order)))
 
     def sqp_work_priority_dev(self, B, info, iter_weight, priority):
         """pmpc_sqp_work_priority_dev: priority (int32 tensor) = iter_weight * iter + qp_solver_iter of info (uint8 tensor of B * 48 bytes)"""
-        f = lib().pmpc_sqp_work_priority_dev
-        f.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
-        _check_status(f(self._ctx, int(B), _dv(info), int(iter_weight), _dv(priority)))
+        _check_status(lib().pmpc_sqp_work_priority_dev(self._ctx, int(B), _dv(info), int(iter_weight), _dv(priority)))
 
     def sqp_solve_batch_prioritised(self, model, P, S, t0, tf, B, d, lbx, ubx, priority=None, lbg=None, ubg=None, x_guess=None, lam_guess=None,
                                     sqp_settings=None, qp_settings=None, mparams=None):
@@ -705,44 +740,29 @@ class Context:
         keep = [_h(a) for a in (mparams, x_guess, lam_guess, d, lbx, ubx, lbg, ubg)]
         pr = None if priority is None else np.ascontiguousarray(priority, dtype=np.int32)
         P_ = C.POINTER(C.c_double)
-        f = lib().pmpc_sqp_solve_batch_prioritised
-        f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, P_, C.c_int, C.c_int] + [P_] * 7 + \
-                     [C.POINTER(SQPSettings), C.POINTER(QPSettings), P_, P_, C.c_void_p, C.c_void_p]
-        _check_status(f(self._ctx, model, P, S, t0, tf, keep[0][1], 0 if keep[0][0] is None else len(keep[0][0]), B,
-                        *[k[1] for k in keep[1:]], C.byref(ss), C.byref(qs), x.ctypes.data_as(P_), lam.ctypes.data_as(P_),
-                        C.c_void_p(info.ctypes.data), None if pr is None else C.c_void_p(pr.ctypes.data)))
+        _check_status(lib().pmpc_sqp_solve_batch_prioritised(
+            self._ctx, model, P, S, t0, tf, keep[0][1], 0 if keep[0][0] is None else len(keep[0][0]), B, *[k[1] for k in keep[1:]], C.byref(ss),
+            C.byref(qs), x.ctypes.data_as(P_), lam.ctypes.data_as(P_), C.c_void_p(info.ctypes.data), None if pr is None else C.c_void_p(pr.ctypes.data)))
         return x, lam, info
 
     def sqp_solve_batch_prioritised_dev(self, model, P, S, t0, tf, B, d, lbx, ubx, x, lam, info, sqp_settings, qp_settings, priority=None, lbg=None,
                                         ubg=None, x_guess=None, lam_guess=None, mparams=None):
         """pmpc_sqp_solve_batch_prioritised_dev on torch CUDA tensors (priority: int32 tensor or None); asynchronous on the context's stream"""
         mk, mp = _h(mparams)
-        P_ = C.POINTER(C.c_double)
-        f = lib().pmpc_sqp_solve_batch_prioritised_dev
-        f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, P_, C.c_int, C.c_int] + [P_] * 7 + \
-                     [C.POINTER(SQPSettings), C.POINTER(QPSettings), P_, P_, C.c_void_p, C.c_void_p]
-        _check_status(f(self._ctx, model, P, S, t0, tf, mp, 0 if mk is None else len(mk), B, _d(x_guess), _d(lam_guess), _d(d),
-                        _d(lbx), _d(ubx), _d(lbg), _d(ubg), C.byref(sqp_settings), C.byref(qp_settings), _d(x), _d(lam),
-                        C.c_void_p(info.data_ptr()), _dv(priority)))
+        _check_status(lib().pmpc_sqp_solve_batch_prioritised_dev(
+            self._ctx, model, P, S, t0, tf, mp, 0 if mk is None else len(mk), B, _d(x_guess), _d(lam_guess), _d(d), _d(lbx), _d(ubx), _d(lbg), _d(ubg),
+            C.byref(sqp_settings), C.byref(qp_settings), _d(x), _d(lam), C.c_void_p(info.data_ptr()), _dv(priority)))
 
     def mpc_step_batch_prioritised_dev(self, model, P, S, t0, tf, B, x0, d, lbx, ubx, x, lam, info, sqp_settings, qp_settings, priority, iter_weight,
                                        u0=None, lbg=None, ubg=None, mparams=None):
         """pmpc_mpc_step_batch_prioritised_dev on torch CUDA tensors: priority (int32 tensor) is read as this step's priorities and overwritten
         with iter_weight * iter + qp_solver_iter of this step's solve"""
         mk, mp = _h(mparams)
-        P_ = C.POINTER(C.c_double)
-        f = lib().pmpc_mpc_step_batch_prioritised_dev
-        f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, P_, C.c_int, C.c_int] + [P_] * 6 + \
-                     [C.POINTER(SQPSettings), C.POINTER(QPSettings), P_, P_, C.c_void_p, P_, C.c_void_p, C.c_int]
-        _check_status(f(self._ctx, model, P, S, t0, tf, mp, 0 if mk is None else len(mk), B, _d(x0), _d(d), _d(lbx), _d(ubx), _d(lbg), _d(ubg),
-                        C.byref(sqp_settings), C.byref(qp_settings), _d(x), _d(lam), C.c_void_p(info.data_ptr()), _d(u0), _dv(priority),
-                        int(iter_weight)))
+        _check_status(lib().pmpc_mpc_step_batch_prioritised_dev(
+            self._ctx, model, P, S, t0, tf, mp, 0 if mk is None else len(mk), B, _d(x0), _d(d), _d(lbx), _d(ubx), _d(lbg), _d(ubg), C.byref(sqp_settings),
+            C.byref(qp_settings), _d(x), _d(lam), C.c_void_p(info.data_ptr()), _d(u0), _dv(priority), int(iter_weight)))
 
     # ------------------------------------------------------------------ trajectories: x(t) / u(t), shifted warm start, regridding (pmpc_traj_*)
-    _TRAJ_SAMPLE_ARGTYPES = [C.c_void_p] + [C.c_int] * 6 + [C.c_double] * 2 + [C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double), C.c_int] + \
-                            [C.POINTER(C.c_double)] * 2
-    _TRAJ_REGRID_ARGTYPES = [C.c_void_p] + [C.c_int] * 8 + [C.c_double] * 2 + [C.POINTER(C.c_double)] * 2
-
     def traj_sample_batch(self, nx, nu, np_, P, S, t0, tf, x, t, per_instance=False, want_x=True, want_u=True):
         """pmpc_traj_sample_batch (host buffers): x (B, n) at the times t — K shared times, or (B, K) with per_instance
         -> xs (B, K, nx), us (B, K, nu); an output that is not wanted is None"""
@@ -752,42 +772,31 @@ class Context:
         assert tk.size == (B * K if per_instance else K)
         xs = np.zeros((B, K, nx)) if want_x else None
         us = np.zeros((B, K, nu)) if want_u else None
-        f = lib().pmpc_traj_sample_batch
-        f.argtypes = self._TRAJ_SAMPLE_ARGTYPES
-        _check_status(f(self._ctx, B, nx, nu, np_, P, S, t0, tf, xp, int(K), tp, 1 if per_instance else 0, _h(xs)[1], _h(us)[1]))
+        _check_status(lib().pmpc_traj_sample_batch(self._ctx, B, nx, nu, np_, P, S, t0, tf, xp, int(K), tp, 1 if per_instance else 0, _h(xs)[1],
+                                                   _h(us)[1]))
         return xs, us
 
     def traj_sample_batch_dev(self, B, nx, nu, np_, P, S, t0, tf, x, K, t, per_instance, xs=None, us=None):
         """pmpc_traj_sample_batch_dev on torch CUDA tensors (xs (B, K, nx) and / or us (B, K, nu)); asynchronous on the context's stream"""
-        f = lib().pmpc_traj_sample_batch_dev
-        f.argtypes = self._TRAJ_SAMPLE_ARGTYPES
-        _check_status(f(self._ctx, int(B), nx, nu, np_, P, S, t0, tf, _d(x), int(K), _d(t), 1 if per_instance else 0, _d(xs), _d(us)))
+        _check_status(lib().pmpc_traj_sample_batch_dev(self._ctx, int(B), nx, nu, np_, P, S, t0, tf, _d(x), int(K), _d(t), 1 if per_instance else 0,
+                                                       _d(xs), _d(us)))
 
     def traj_shift_batch_dev(self, B, nx, nu, np_, ng, P, S, t0, tf, dt, x, lam=None):
         """pmpc_traj_shift_batch_dev on torch CUDA tensors, in place (lam: the duals, or None); asynchronous on the context's stream"""
-        f = lib().pmpc_traj_shift_batch_dev
-        f.argtypes = [C.c_void_p] + [C.c_int] * 7 + [C.c_double] * 3 + [C.POINTER(C.c_double)] * 2
-        _check_status(f(self._ctx, int(B), nx, nu, np_, ng, P, S, t0, tf, float(dt), _d(x), _d(lam)))
+        _check_status(lib().pmpc_traj_shift_batch_dev(self._ctx, int(B), nx, nu, np_, ng, P, S, t0, tf, float(dt), _d(x), _d(lam)))
 
     def traj_regrid_batch(self, nx, nu, np_, P, S, P2, S2, t0, tf, x):
         """pmpc_traj_regrid_batch (host buffers): x (B, n) of the (P, S) grid -> (B, n2) on the (P2, S2) grid"""
         xk, xp = _h(np.atleast_2d(x)); B = xk.shape[0]
         out = np.zeros((B, (nx + nu) * (P2 * S2 + 1) + np_))
-        f = lib().pmpc_traj_regrid_batch
-        f.argtypes = self._TRAJ_REGRID_ARGTYPES
-        _check_status(f(self._ctx, B, nx, nu, np_, P, S, P2, S2, t0, tf, xp, _h(out)[1]))
+        _check_status(lib().pmpc_traj_regrid_batch(self._ctx, B, nx, nu, np_, P, S, P2, S2, t0, tf, xp, _h(out)[1]))
         return out
 
     def traj_regrid_batch_dev(self, B, nx, nu, np_, P, S, P2, S2, t0, tf, x_src, x_dst):
         """pmpc_traj_regrid_batch_dev on torch CUDA tensors; asynchronous on the context's stream"""
-        f = lib().pmpc_traj_regrid_batch_dev
-        f.argtypes = self._TRAJ_REGRID_ARGTYPES
-        _check_status(f(self._ctx, int(B), nx, nu, np_, P, S, P2, S2, t0, tf, _d(x_src), _d(x_dst)))
+        _check_status(lib().pmpc_traj_regrid_batch_dev(self._ctx, int(B), nx, nu, np_, P, S, P2, S2, t0, tf, _d(x_src), _d(x_dst)))
 
     # ------------------------------------------------------------------ the plant of a closed loop (pmpc_plant_*)
-    _PLANT_ARGTYPES = [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_double,
-                       C.POINTER(PlantSettings)] + [C.POINTER(C.c_double)] * 5
-
     def plant_step_batch(self, model, P, S, t0, tf, dt, state, u0=None, iterate=None, d=None, w=None, settings=None, mparams=None):
         """pmpc_plant_step_batch (host buffers): state (B, nx) advanced by one control period dt with the model's own dynamics -> a new array.
         u0 (B, nu) for control 0; iterate (B, n) when the model has parameters or for control 1; d (B, nd): the PLANT's static parameters;
@@ -795,19 +804,16 @@ class Context:
         sk = np.array(np.atleast_2d(state), dtype=np.float64, order="C")
         mk, mp = _h(mparams)
         keep = [_h(a) for a in (u0, iterate, d, w)]
-        f = lib().pmpc_plant_step_batch
-        f.argtypes = self._PLANT_ARGTYPES
-        _check_status(f(self._ctx, int(model), mp, 0 if mk is None else len(mk), int(P), int(S), float(t0), float(tf), sk.shape[0], float(dt),
-                        C.byref(settings or plant_settings_default()), _h(sk)[1], *[k[1] for k in keep]))
+        _check_status(lib().pmpc_plant_step_batch(self._ctx, int(model), mp, 0 if mk is None else len(mk), int(P), int(S), float(t0), float(tf), sk.shape[0],
+                                                  float(dt), C.byref(settings or plant_settings_default()), _h(sk)[1], *[k[1] for k in keep]))
         return sk
 
     def plant_step_batch_dev(self, model, P, S, t0, tf, B, dt, state, u0=None, iterate=None, d=None, w=None, settings=None, mparams=None):
         """pmpc_plant_step_batch_dev on torch CUDA tensors: state (B, nx) advanced in place; asynchronous on the context's stream"""
         mk, mp = _h(mparams)
-        f = lib().pmpc_plant_step_batch_dev
-        f.argtypes = self._PLANT_ARGTYPES
-        _check_status(f(self._ctx, int(model), mp, 0 if mk is None else len(mk), int(P), int(S), float(t0), float(tf), int(B), float(dt),
-                        C.byref(settings or plant_settings_default()), _d(state), _d(u0), _d(iterate), _d(d), _d(w)))
+        _check_status(lib().pmpc_plant_step_batch_dev(self._ctx, int(model), mp, 0 if mk is None else len(mk), int(P), int(S), float(t0), float(tf), int(B),
+                                                      float(dt), C.byref(settings or plant_settings_default()), _d(state), _d(u0), _d(iterate), _d(d),
+                                                      _d(w)))
 
     def mpc_batch(self, model, P, S, t0, tf, B, d, lbx, ubx, lbg=None, ubg=None, x_guess=None, lam_guess=None, mparams=None):
         """pmpc_mpc_batch_create: B controllers whose data stay on the device between steps (MPCBatch)"""
@@ -824,9 +830,8 @@ class Context:
         cost = np.zeros(B); c = np.zeros((B, max(m, 1))); jac = np.zeros((B, max(m, 1) * nx)); cg = np.zeros((B, nx)); lg = np.zeros((B, nx))
         lh = np.zeros((B, nx * nx))
         P_ = C.POINTER(C.c_double)
-        f = lib().pmpc_nlp_linearise_batch
-        f.argtypes = [C.c_void_p, C.c_int, C.c_int] + [P_] * 9
-        _check_status(f(self._ctx, int(problem), B, xp, lp, dp_, *[a.ctypes.data_as(P_) for a in (cost, c, jac, cg, lg, lh)]))
+        _check_status(lib().pmpc_nlp_linearise_batch(self._ctx, int(problem), B, xp, lp, dp_,
+                                                     *[a.ctypes.data_as(P_) for a in (cost, c, jac, cg, lg, lh)]))
         return dict(cost=cost, c=c[:, :m], jac=jac[:, :m * nx].reshape(B, nx, m).transpose(0, 2, 1).copy(), cost_grad=cg, lag_grad=lg,
                     lag_hess=lh.reshape(B, nx, nx).transpose(0, 2, 1).copy())
 
@@ -834,26 +839,18 @@ class Context:
                         qp_settings=None):
         """pmpc_nlp_solve_batch (host buffers) -> x (B, nx), lam (B, m + nx), info (SQP_INFO_DTYPE); None inputs take the defaults of the
         C entry point (zeros; -inf / +inf bounds)"""
-        f = lib().pmpc_nlp_solve_batch
-        f.argtypes = [C.c_void_p, C.c_int, C.c_int] + _NLP_SOLVE_ARGTYPES
-        return _nlp_host_call(f, (self._ctx, int(problem)), B, nlp_dims(problem), x_guess, lam_guess, d, lbx, ubx, lbg, ubg, sqp_settings,
-                              qp_settings)
+        return _nlp_host_call(lib().pmpc_nlp_solve_batch, (self._ctx, int(problem)), B, nlp_dims(problem), x_guess, lam_guess, d, lbx, ubx, lbg, ubg,
+                              sqp_settings, qp_settings)
 
     def nlp_solve_batch_dev(self, problem, B, x, lam, info, sqp_settings, qp_settings, x_guess=None, lam_guess=None, d=None, lbx=None, ubx=None,
                             lbg=None, ubg=None):
         """pmpc_nlp_solve_batch_dev on torch CUDA tensors (info: a uint8 tensor of B * 48 bytes); asynchronous on the context's stream"""
-        f = lib().pmpc_nlp_solve_batch_dev
-        f.argtypes = [C.c_void_p, C.c_int, C.c_int] + _NLP_SOLVE_ARGTYPES
-        _check_status(f(self._ctx, int(problem), int(B), _d(x_guess), _d(lam_guess), _d(d), _d(lbx), _d(ubx), _d(lbg), _d(ubg),
-                        C.byref(sqp_settings), C.byref(qp_settings), _d(x), _d(lam), C.c_void_p(info.data_ptr())))
+        _check_status(lib().pmpc_nlp_solve_batch_dev(self._ctx, int(problem), int(B), _d(x_guess), _d(lam_guess), _d(d), _d(lbx), _d(ubx), _d(lbg), _d(ubg),
+                                                     C.byref(sqp_settings), C.byref(qp_settings), _d(x), _d(lam), C.c_void_p(info.data_ptr())))
 
     def sqp_solve_batch_dev(self, model, P, S, t0, tf, B, d, lbx, ubx, x, lam, info, sqp_settings, qp_settings, lbg=None,
                             ubg=None, x_guess=None, lam_guess=None, mparams=None):
         mk, mp = _h(mparams)
-        P_ = C.POINTER(C.c_double)
-        f = lib().pmpc_sqp_solve_batch_dev
-        f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, P_, C.c_int, C.c_int] + [P_] * 7 + \
-                     [C.POINTER(SQPSettings), C.POINTER(QPSettings), P_, P_, C.c_void_p]
-        _check(f(self._ctx, model, P, S, t0, tf, mp, 0 if mk is None else len(mk), B, _d(x_guess), _d(lam_guess), _d(d),
-                 _d(lbx), _d(ubx), _d(lbg), _d(ubg), C.byref(sqp_settings), C.byref(qp_settings), _d(x), _d(lam),
-                 C.c_void_p(info.data_ptr())))
+        _check(lib().pmpc_sqp_solve_batch_dev(self._ctx, model, P, S, t0, tf, mp, 0 if mk is None else len(mk), B, _d(x_guess), _d(lam_guess), _d(d),
+                                              _d(lbx), _d(ubx), _d(lbg), _d(ubg), C.byref(sqp_settings), C.byref(qp_settings), _d(x), _d(lam),
+                                              C.c_void_p(info.data_ptr())))

@@ -1,12 +1,16 @@
 """CPU-side checks of the product boundary: the C-ABI library loads, exports every symbol include/polympc_amd.h declares,
 refuses to run without a GPU (no fallback), and its host-side collocation constants match the pinned oracle."""
+import ctypes
 import os
 import re
+import sys
 
 import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import abi_header  # noqa: E402
 
 
 @pytest.fixture(scope="module")
@@ -25,6 +29,29 @@ def test_header_symbols_are_exported(pa):
     lib = pa.lib()
     for name in declared:
         assert hasattr(lib, name), f"{name} is declared in include/polympc_amd.h but not exported"
+
+
+def test_ctypes_signatures_match_the_header(pa):
+    """Every function the header declares has one entry in capi.SIGNATURES, with the header's return type and, argument for argument, the ctypes
+    type abi_header.ctype_of gives the declaration: ctypes itself never complains about a wrong list."""
+    assert abi_header.mismatches(pa.capi.SIGNATURES, pa) == []
+    assert sorted(pa.capi.SIGNATURES) == sorted(abi_header.declarations())
+
+
+def test_the_header_check_reports_a_doctored_table(pa):
+    C = ctypes
+    table = lambda: {name: (ret, list(args)) for name, (ret, args) in pa.capi.SIGNATURES.items()}   # a copy to doctor
+    swapped = table()
+    k = swapped["pmpc_traj_shift_batch_dev"][1].index(C.c_int)
+    swapped["pmpc_traj_shift_batch_dev"][1][k] = C.c_double
+    short = table()
+    short["pmpc_mpc_step_batch_user_dev"][1].pop()
+    removed = table()
+    del removed["pmpc_nlp_dims"]
+    for doctored, name, what in ((swapped, "pmpc_traj_shift_batch_dev", f"argument {k} "), (short, "pmpc_mpc_step_batch_user_dev", "27 parameters"),
+                                 (removed, "pmpc_nlp_dims", "only in the header")):
+        got = abi_header.mismatches(doctored, pa)
+        assert len(got) == 1 and got[0].startswith(name + ":") and what in got[0], got
 
 
 def test_struct_layouts_match_header(pa):
@@ -105,7 +132,6 @@ def test_argument_validation_without_a_device():
     one = (C.c_double * 64)()
     info = (C.c_char * 48)()
     f = L.pmpc_sqp_solve_batch_dev
-    f.restype = C.c_int
     args = lambda ctx, d, s: (ctx, 0, 6, 1, C.c_double(0.0), C.c_double(2.0), None, 0, 1, None, None, d, one, one, None, None, C.byref(s), C.byref(qs), one, one, info)
     fake = C.c_void_p(8)   # never dereferenced: validation precedes every use of the context
     assert f(*args(None, one, ss)) == 1                       # PMPC_ERR_INVALID_ARGUMENT: NULL context
@@ -116,9 +142,6 @@ def test_argument_validation_without_a_device():
     P_ = C.POINTER(C.c_double)
     dbl = lambda v: C.cast(v, P_)
     g = L.pmpc_sqp_solve_batch
-    g.restype = C.c_int
-    g.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, P_, C.c_int, C.c_int] + [P_] * 7 + \
-                 [C.POINTER(pa.SQPSettings), C.POINTER(pa.QPSettings), P_, P_, C.c_void_p]
     hargs = lambda d, s: (fake, 0, 6, 1, 0.0, 2.0, None, 0, 1, None, None, d, dbl(one), dbl(one), None, None, C.byref(s), C.byref(qs), dbl(one), dbl(one), info)
 
     def sqp_with(**kw):
@@ -137,10 +160,7 @@ def test_argument_validation_without_a_device():
                           ("pmpc_qp_boxadmm_solve_batch_f32", flt, C.c_float), ("pmpc_qp_admm_solve_batch_f32", flt, C.c_float)]:
         for suffix in ("", "_dev"):
             e = getattr(L, name + suffix)
-            e.restype = C.c_int
-            PT = C.POINTER(T_)
-            e.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int] + [PT] * 9 + [C.POINTER(pa.QPSettings)] + [PT] * 2 + [C.c_void_p]
-            p = C.cast(buf, PT)
+            p = C.cast(buf, C.POINTER(T_))
             call = lambda m, A, x0, y0, s: e(fake, 1, 2, m, p, p, A, p, p, p, p, x0, y0, C.byref(s), p, p, info)
             assert call(1, None, None, None, q) == 1, name + suffix        # m > 0 and A == NULL
             assert call(1, p, p, None, q) == 1, name + suffix              # x0 without y0
@@ -151,7 +171,5 @@ def test_argument_validation_without_a_device():
         assert getattr(L, name)(fake, 1, 2, 1, p, p, p, p, p, p, p, None, None, C.byref(q2), p, p, info) == 1, name
     # generic NLP: a setting nlp_check_settings refuses
     nl = L.pmpc_nlp_solve_batch
-    nl.restype = C.c_int
-    nl.argtypes = [C.c_void_p, C.c_int, C.c_int] + [P_] * 7 + [C.POINTER(pa.SQPSettings), C.POINTER(pa.QPSettings), P_, P_, C.c_void_p]
     for bad in (dict(hessian_update=1), dict(line_search=1), dict(regularisation=3)):
         assert nl(fake, pa.NLP_HS071, 1, None, None, None, None, None, None, None, C.byref(sqp_with(**bad)), C.byref(qs), dbl(one), dbl(one), info) == 1, bad

@@ -3,10 +3,13 @@ polympc_amd/capi.py match include/polympc_amd.h argument for argument, and the n
 import ctypes as C
 import os
 import re
+import sys
 
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import abi_header  # noqa: E402
 NEW = ("pmpc_dispatch_order_dev", "pmpc_sqp_work_priority_dev", "pmpc_sqp_solve_batch_prioritised", "pmpc_sqp_solve_batch_prioritised_dev",
        "pmpc_mpc_step_batch_prioritised_dev", "pmpc_mpc_batch_set_dispatch")
 
@@ -18,18 +21,6 @@ def pa():
     return polympc_amd
 
 
-def _declarations():
-    """name -> list of parameter type classes ('int', 'double', 'ptr') from the header"""
-    hdr = open(os.path.join(ROOT, "include", "polympc_amd.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    out = {}
-    for name in NEW:
-        m = re.search(r"pmpc_status\s+" + name + r"\s*\(([^;]*)\)\s*;", hdr)
-        assert m, f"{name} is not declared in include/polympc_amd.h"
-        out[name] = ["ptr" if "*" in p else p.split()[-2] for p in (q.strip() for q in m.group(1).split(","))]
-    return out
-
-
 def test_new_entry_points_are_declared_exported_and_listed(pa):
     lib = pa.lib()
     for name in NEW:
@@ -38,39 +29,14 @@ def test_new_entry_points_are_declared_exported_and_listed(pa):
     assert C.sizeof(pa.SQPSettings) == 112                       # and add no settings field
 
 
-def test_ctypes_signatures_match_the_header(pa, monkeypatch):
-    """Every Python wrapper sets argtypes before it calls: run each wrapper against a recording stand-in of the library and compare what it set
-    with the header's parameter list."""
-    want = _declarations()
-    seen = {}
-
-    class Fn:
-        def __init__(self, name):
-            self.name, self.argtypes, self.restype = name, None, C.c_int
-
-        def __call__(self, *args):
-            seen[self.name] = (list(self.argtypes), len(args))
-            return 0
-
-    class Lib:
-        def __init__(self, real):
-            self._real, self._fns = real, {}
-
-        def __getattr__(self, name):
-            if name in NEW or name in ("pmpc_mpc_batch_create", "pmpc_mpc_batch_destroy"):
-                return self._fns.setdefault(name, Fn(name))
-            return getattr(self._real, name)
-
-    fake = Lib(pa.lib())
+def test_every_entry_point_is_reached_by_a_wrapper(pa, monkeypatch):
+    """Run every Python wrapper against a recording stand-in of the library: each entry point is called, with the header's number of arguments,
+    each of a kind its declared type accepts (the types themselves: test_capi_cpu.test_ctypes_signatures_match_the_header)."""
+    fake = abi_header.RecordingLib(pa, NEW + ("pmpc_mpc_batch_create", "pmpc_mpc_batch_destroy"))
     monkeypatch.setattr(pa.capi, "lib", lambda: fake)
-
-    class T:   # stands in for a torch CUDA tensor
-        is_cuda, is_contiguous = True, staticmethod(lambda: True)
-        data_ptr = staticmethod(lambda: 64)
-
     ctx = pa.Context.__new__(pa.Context); ctx._ctx = C.c_void_p(8)
     ss, qs = pa.SQPSettings(), pa.QPSettings()
-    t = T()
+    t = abi_header.FakeTensor()
     ctx.dispatch_order_dev(4, t, t)
     ctx.sqp_work_priority_dev(4, t, 64, t)
     ctx.sqp_solve_batch_prioritised(0, 6, 1, 0.0, 2.0, 1, [[2.0]], [[0.0] * 35], [[0.0] * 35], priority=[1], sqp_settings=ss, qp_settings=qs)
@@ -80,19 +46,9 @@ def test_ctypes_signatures_match_the_header(pa, monkeypatch):
     b.set_dispatch(1, 64)
     b._batch = C.c_void_p()
     ctx._ctx = C.c_void_p()   # (nothing to destroy)
-
-    def kind(ct):
-        if ct is C.c_int:
-            return "int"
-        if ct is C.c_double:
-            return "double"
-        assert ct is C.c_void_p or issubclass(ct, C._Pointer), ct
-        return "ptr"
     for name in NEW:
-        assert name in seen, f"no Python wrapper called {name}"
-        argtypes, nargs = seen[name]
-        assert [kind(a) for a in argtypes] == want[name], name
-        assert nargs == len(want[name]), name
+        assert name in fake.calls, f"no Python wrapper called {name}"
+        assert fake.calls[name] == len(abi_header.declarations()[name][1]), name
 
 
 def test_argument_validation_without_a_device(pa):
@@ -104,8 +60,6 @@ def test_argument_validation_without_a_device(pa):
     iv = C.cast(ints, C.c_void_p)
     fake = C.c_void_p(8)
     qs = pa.qp_settings_sqp_default()
-    sqp_args = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, P_, C.c_int, C.c_int] + [P_] * 7 + \
-               [C.POINTER(pa.SQPSettings), C.POINTER(pa.QPSettings), P_, P_, C.c_void_p, C.c_void_p]
 
     def sqp_with(**kw):
         s = pa.sqp_settings_default()
@@ -116,7 +70,6 @@ def test_argument_validation_without_a_device(pa):
                     dict(filter_state=8), dict(iteration_trace=8, iteration_trace_capacity=4))
     for name in ("pmpc_sqp_solve_batch_prioritised", "pmpc_sqp_solve_batch_prioritised_dev"):
         f = getattr(L, name)
-        f.restype, f.argtypes = C.c_int, sqp_args
         call = lambda c, d, s, B=1, pr=iv: f(c, 0, 6, 1, 0.0, 2.0, None, 0, B, None, None, d, dbl(one), dbl(one), None, None, C.byref(s), C.byref(qs),
                                              dbl(one), dbl(one), info, pr)
         ok = pa.sqp_settings_default()
@@ -130,9 +83,6 @@ def test_argument_validation_without_a_device(pa):
         assert f(fake, 9, 6, 1, 0.0, 2.0, None, 0, 1, None, None, dbl(one), dbl(one), dbl(one), None, None, C.byref(ok), C.byref(qs), dbl(one), dbl(one),
                  info, iv) == 5, name                              # PMPC_ERR_UNKNOWN_MODEL
     g = L.pmpc_mpc_step_batch_prioritised_dev
-    g.restype = C.c_int
-    g.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, P_, C.c_int, C.c_int] + [P_] * 6 + \
-                 [C.POINTER(pa.SQPSettings), C.POINTER(pa.QPSettings), P_, P_, C.c_void_p, P_, C.c_void_p, C.c_int]
     step = lambda c, x0, d, s, B=1: g(c, 0, 6, 1, 0.0, 2.0, None, 0, B, x0, d, dbl(one), dbl(one), None, None, C.byref(s), C.byref(qs), dbl(one), dbl(one),
                                      info, dbl(one), iv, 64)
     ok = pa.sqp_settings_default()
@@ -141,13 +91,10 @@ def test_argument_validation_without_a_device(pa):
         assert step(fake, dbl(one), dbl(one), sqp_with(**bad)) == 1, bad
     assert step(fake, dbl(one), dbl(one), ok, B=0) == 0
     o = L.pmpc_dispatch_order_dev
-    o.restype, o.argtypes = C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     assert o(None, 1, iv, iv) == 1 and o(fake, 1, iv, None) == 1 and o(fake, -1, iv, iv) == 1 and o(fake, 0, iv, iv) == 0
     w = L.pmpc_sqp_work_priority_dev
-    w.restype, w.argtypes = C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
     assert w(None, 1, info, 64, iv) == 1 and w(fake, 1, None, 64, iv) == 1 and w(fake, 1, info, 64, None) == 1 and w(fake, 0, info, 64, iv) == 0
     sd = L.pmpc_mpc_batch_set_dispatch
-    sd.restype, sd.argtypes = C.c_int, [C.c_void_p, C.c_int, C.c_int]
     assert sd(None, 1, 64) == 1 and sd(fake, 2, 64) == 1 and sd(fake, -1, 0) == 1   # (a bad mode is refused before the handle is read)
 
 

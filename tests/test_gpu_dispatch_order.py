@@ -315,6 +315,5 @@ def test_empty_batch_and_null_arguments(pa, ctx):
     one = torch.zeros(8, dtype=torch.int32, device="cuda:0")
     ctx.dispatch_order_dev(0, one, one)   # B == 0: nothing happens
     f = L.pmpc_dispatch_order_dev
-    f.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     assert f(ctx._ctx, 4, C.c_void_p(one.data_ptr()), None) == ERR_INVALID_ARGUMENT
     assert f(ctx._ctx, -1, None, C.c_void_p(one.data_ptr())) == ERR_INVALID_ARGUMENT

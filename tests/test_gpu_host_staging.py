@@ -65,10 +65,9 @@ def _qp_dev(pa, ctx, entry, q, s, x0=None, y0=None):
     x = torch.zeros(B, n, dtype=tdt, device="cuda:0"); y = torch.zeros(B, n + m, dtype=tdt, device="cuda:0")
     info = torch.zeros(B, 40, dtype=torch.uint8, device="cuda:0")
     torch.cuda.synchronize()
-    f = getattr(pa.lib(), entry + "_dev")
-    f.restype = C.c_int
-    f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 9 + [C.POINTER(pa.QPSettings)] + [C.c_void_p] * 3
-    st = f(ctx._ctx, B, n, m, *[_ptr(t) for t in ins], C.byref(s), _ptr(x), _ptr(y), _ptr(info))
+    PT = C.POINTER(C.c_float if dt == np.float32 else C.c_double)
+    typed = lambda t: None if _ptr(t) is None else C.cast(_ptr(t), PT)
+    st = getattr(pa.lib(), entry + "_dev")(ctx._ctx, B, n, m, *[typed(t) for t in ins], C.byref(s), typed(x), typed(y), _ptr(info))
     assert st == 0, (entry, st)
     ctx.synchronize()
     return x.cpu().numpy(), y.cpu().numpy(), info.cpu().numpy().view(pa.capi.QP_INFO_DTYPE).reshape(B)
@@ -287,9 +286,6 @@ def test_osqp_form_refused_past_the_lds_limit(pa, ctx):
     P_ = C.POINTER(C.c_double)
     p = lambda a: np.ascontiguousarray(a).ctypes.data_as(P_)
     s = pa.qp_settings_default()
-    f = pa.lib().pmpc_qp_admm_solve_batch
-    f.restype = C.c_int
-    f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int] + [P_] * 9 + [C.POINTER(pa.QPSettings), P_, P_, C.c_void_p]
-    st = f(ctx._ctx, 1, n, m, *[p(q[k]) for k in QP_KEYS], None, None, C.byref(s), p(x), p(y), C.c_void_p(info.ctypes.data))
+    st = pa.lib().pmpc_qp_admm_solve_batch(ctx._ctx, 1, n, m, *[p(q[k]) for k in QP_KEYS], None, None, C.byref(s), p(x), p(y), C.c_void_p(info.ctypes.data))
     assert st == ERR_UNSUPPORTED_SIZE
     assert np.all(x == 7.0) and np.all(y == 7.0) and np.all(info == 7)

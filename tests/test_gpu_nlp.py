@@ -236,10 +236,8 @@ def test_nlp_refuses_filter_state_iteration_trace_unknown_id_and_65_rows(ctx, pa
         ctx.nlp_solve_batch(9, 1, sqp_settings=ss)
     assert e.value.status == 5   # PMPC_ERR_UNKNOWN_MODEL (the binding asks pmpc_nlp_dims first) ...
     f = pa.lib().pmpc_nlp_solve_batch   # ... and the C entry point itself
-    f.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 12
-    out = C.cast(buf, C.c_void_p)
     qs = pa.qp_settings_sqp_default()
-    assert f(ctx._ctx, 9, 1, None, None, None, None, None, None, None, C.addressof(ss), C.addressof(qs), out, out, out) == 5
+    assert f(ctx._ctx, 9, 1, None, None, None, None, None, None, None, C.byref(ss), C.byref(qs), buf, buf, C.cast(buf, C.c_void_p)) == 5
     wide = pa.capi.UserNLP(user_so, "Wide65")
     with pytest.raises(pa.capi.StatusError) as e:   # host wrapper
         wide.solve_batch(ctx, 2, sqp_settings=ss)

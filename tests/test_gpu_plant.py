@@ -297,7 +297,6 @@ def test_refusals_that_need_a_live_batch(pa, ctx):
         b.rollout(pr["state"], 2, 0.05, ss, qs)
     assert e.value.status == INVALID
     sp = pa.lib().pmpc_mpc_batch_set_plant
-    sp.restype, sp.argtypes = C.c_int, [C.c_void_p, C.POINTER(pa.PlantSettings), C.POINTER(C.c_double), C.c_void_p]
     user = pa.UserOCP(SO, "UserRobot", model=struct.pack("<d", 1.0))
     assert sp(b._batch, C.byref(pa.plant_settings_default()), None, C.cast(user.plant_fn, C.c_void_p)) == INVALID
     ub = user.mpc_batch(ctx, 6, 1, 0.0, TF, 3, pr["d"], pr["lbx"], pr["ubx"])

@@ -3,13 +3,15 @@ without a GPU: every refusal include/polympc_amd.h lists is answered before any 
 the header's declarations, and UserOCP reads the dimensions of the two OCPs registered in tests/cpp/user_ocp.hip."""
 import ctypes as C
 import os
-import re
 import subprocess
+import sys
 
 import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
+sys.path.insert(0, HERE)
+import abi_header  # noqa: E402
+
 CPP = os.path.join(HERE, "cpp")
 SO = os.path.join(CPP, "libuser_ocp.so")
 INVALID = 1
@@ -29,15 +31,6 @@ def user_lib(pa):
     return SO
 
 
-def _step_argtypes(pa):
-    return [C.c_void_p] * 3 + [C.c_int] * 7 + [C.c_double] * 2 + [C.c_int] + [P_] * 6 + [C.POINTER(pa.SQPSettings), C.POINTER(pa.QPSettings), P_, P_, C.c_void_p,
-                                                                                         P_, C.c_void_p, C.c_int]
-
-
-def _create_argtypes():
-    return [C.c_void_p] * 3 + [C.c_ulong] + [C.c_int] * 7 + [C.c_double] * 2 + [C.c_int] + [P_] * 7 + [C.POINTER(C.c_void_p)]
-
-
 FAKE = 8   # a non-NULL context / function / model pointer that validation never dereferences
 
 
@@ -55,10 +48,7 @@ def _step_call(pa, ss=_DEFAULT, qs=_DEFAULT, **kw):
              ss=None if ss is None else C.byref(ss), qs=None if qs is None else C.byref(qs), x=p, lam=p, info=C.cast(one, C.c_void_p), u0=p,
              priority=None, iter_weight=0)
     a.update(kw)
-    f = pa.lib().pmpc_mpc_step_batch_user_dev
-    f.restype = C.c_int
-    f.argtypes = _step_argtypes(pa)
-    return f(*a.values())
+    return pa.lib().pmpc_mpc_step_batch_user_dev(*a.values())
 
 
 def _create_call(pa, **kw):
@@ -68,10 +58,7 @@ def _create_call(pa, **kw):
     a = dict(ctx=FAKE, fn=FAKE, model=FAKE, model_bytes=8, nx=2, nu=1, np=0, nd=1, ng=1, P=5, S=2, t0=0.0, tf=2.0, B=1, d=p, lbx=p, ubx=p, lbg=p, ubg=p,
              x_guess=None, lam_guess=None, batch=C.byref(out))
     a.update(kw)
-    f = pa.lib().pmpc_mpc_batch_create_user
-    f.restype = C.c_int
-    f.argtypes = _create_argtypes()
-    st = f(*a.values())
+    st = pa.lib().pmpc_mpc_batch_create_user(*a.values())
     assert not out.value, "a refused create must not hand out a batch"
     return st
 
@@ -111,51 +98,24 @@ CREATE_REFUSALS = [dict(ctx=None), dict(fn=None), dict(model=None), dict(model_b
 @pytest.mark.parametrize("bad", CREATE_REFUSALS, ids=lambda b: "%s=%s" % next(iter(b.items())))
 def test_create_refuses_before_any_device_call(pa, bad):
     if "batch" in bad:
-        f = pa.lib().pmpc_mpc_batch_create_user
-        f.restype = C.c_int
-        f.argtypes = _create_argtypes()
         p = C.cast((C.c_double * 64)(), P_)
-        assert f(FAKE, FAKE, FAKE, 8, 2, 1, 0, 1, 1, 5, 2, 0.0, 2.0, 1, p, p, p, p, p, None, None, None) == INVALID
+        assert pa.lib().pmpc_mpc_batch_create_user(FAKE, FAKE, FAKE, 8, 2, 1, 0, 1, 1, 5, 2, 0.0, 2.0, 1, p, p, p, p, p, None, None, None) == INVALID
         return
     assert _create_call(pa, **bad) == INVALID
 
 
 def test_update_and_the_handle_entries_refuse_a_null_batch(pa):
-    L = pa.lib()
-    f = L.pmpc_mpc_batch_update
-    f.restype = C.c_int
-    f.argtypes = [C.c_void_p] + [P_] * 5
-    assert f(None, None, None, None, None, None) == INVALID
+    assert pa.lib().pmpc_mpc_batch_update(None, None, None, None, None, None) == INVALID
 
 
-def _header_params(name):
-    hdr = open(os.path.join(ROOT, "include", "polympc_amd.h")).read()
-    m = re.search(r"pmpc_status\s+" + name + r"\s*\(([^;]*)\)\s*;", hdr)
-    assert m, name + " is not declared in include/polympc_amd.h"
-    return [" ".join(p.split()) for p in m.group(1).split(",")]
-
-
-def _ctype_of(param, pa):
-    """the ctypes type of one C parameter declaration of the header"""
-    if "*" in param:
-        base = param.replace("const ", "").split("*")[0].strip()
-        stars = param.count("*")
-        if base == "double" and stars == 1:
-            return P_
-        if base == "pmpc_sqp_settings":
-            return C.POINTER(pa.SQPSettings)
-        if base == "pmpc_qp_settings":
-            return C.POINTER(pa.QPSettings)
-        if base == "pmpc_mpc_batch" and stars == 2:
-            return C.POINTER(C.c_void_p)
-        return C.c_void_p   # pmpc_context*, const void*, pmpc_sqp_info*, int*, pmpc_mpc_batch*
-    return {"int": C.c_int, "double": C.c_double, "unsigned long": C.c_ulong, "pmpc_sqp_dev_fn": C.c_void_p}[param.rsplit(" ", 1)[0]]
-
-
-def test_ctypes_argument_lists_are_the_headers(pa):
-    """The argument lists polympc_amd/capi.py gives the three entry points (left on the functions by a refused call) against the declarations."""
-    L = pa.lib()
-    so = pa.UserOCP.__new__(pa.UserOCP)   # no library needed: only the argument lists are asked for
+def test_wrappers_reach_the_entry_points_and_are_refused(pa, monkeypatch):
+    """The Python wrappers of the three entry points with a NULL context / batch: each reaches its entry point with the header's number of
+    arguments, each of a kind its declared type accepts (the types themselves: test_capi_cpu.test_ctypes_signatures_match_the_header), and the
+    library refuses the call before any device call."""
+    names = ("pmpc_mpc_step_batch_user_dev", "pmpc_mpc_batch_create_user", "pmpc_mpc_batch_update")
+    fake = abi_header.RecordingLib(pa, names, passthrough=True)
+    monkeypatch.setattr(pa.capi, "lib", lambda: fake)
+    so = pa.UserOCP.__new__(pa.UserOCP)   # no library needed: every call is refused
     so.fn = C.c_void_p(FAKE); so.model = C.create_string_buffer(8); so.model_bytes = 8
     so.nx, so.nu, so.np, so.nd, so.ng = 2, 1, 0, 1, 1
 
@@ -169,11 +129,11 @@ def test_ctypes_argument_lists_are_the_headers(pa):
         assert e.value.status == INVALID
     batch = pa.MPCBatch.__new__(pa.MPCBatch)
     batch._batch = C.c_void_p(); batch.B = 1; batch.dims = so.dims(5, 2)
-    with pytest.raises(pa.StatusError):
+    with pytest.raises(pa.StatusError) as e:
         batch.update()
-    for name in ("pmpc_mpc_step_batch_user_dev", "pmpc_mpc_batch_create_user", "pmpc_mpc_batch_update"):
-        want = [_ctype_of(p, pa) for p in _header_params(name)]
-        assert list(getattr(L, name).argtypes) == want, name
+    assert e.value.status == INVALID
+    for name in names:
+        assert fake.calls.get(name) == len(abi_header.declarations()[name][1]), name
 
 
 class _NoTensor:

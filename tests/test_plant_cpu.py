@@ -17,6 +17,7 @@ import pytest
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 sys.path.insert(0, HERE)
+import abi_header  # noqa: E402
 import plant_ref  # noqa: E402
 
 CPP = os.path.join(HERE, "cpp")
@@ -117,7 +118,6 @@ def test_argument_validation_without_a_device(pa):
     the state keeps what it held."""
     L = pa.lib()
     P_ = C.POINTER(C.c_double)
-    PS = C.POINTER(pa.PlantSettings)
     MARK = -77.25
     fake = C.c_void_p(8)
     state = (C.c_double * 16)(*([MARK] * 16)); u0 = (C.c_double * 16)(*([0.5] * 16)); it = (C.c_double * 64)(*([1.0] * 64))
@@ -149,8 +149,6 @@ def test_argument_validation_without_a_device(pa):
 
     for name in ("pmpc_plant_step_batch", "pmpc_plant_step_batch_dev"):
         f = getattr(L, name)
-        f.restype = C.c_int
-        f.argtypes = [C.c_void_p, C.c_int, P_, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_double, PS] + [P_] * 5
         ok = dict(c=fake, model=0, P=6, S=1, t0=0.0, tf=2.0, B=1, dt=0.05, s=mk(), state=p(state), u0=p(u0), it=p(it), d=p(d), w=p(w))
 
         def call(f=f, ok=ok, **kw):
@@ -161,8 +159,6 @@ def test_argument_validation_without_a_device(pa):
 
     for name in ("pmpc_plant_step_batch_user", "pmpc_plant_step_batch_user_dev"):
         f = getattr(L, name)
-        f.restype = C.c_int
-        f.argtypes = [C.c_void_p] * 3 + [C.c_int] * 6 + [C.c_double] * 2 + [C.c_int, C.c_double, PS] + [P_] * 5
         ok = dict(c=fake, fn=fake, m=fake, nx=3, nu=2, np=0, nd=1, P=6, S=1, t0=0.0, tf=2.0, B=1, dt=0.05, s=mk(), state=p(state), u0=p(u0), it=p(it),
                   d=p(d), w=p(w))
 
@@ -173,14 +169,11 @@ def test_argument_validation_without_a_device(pa):
         checks(call, True)
 
     sp = L.pmpc_mpc_batch_set_plant
-    sp.restype, sp.argtypes = C.c_int, [C.c_void_p, PS, P_, C.c_void_p]
     assert sp(None, C.byref(mk()), None, None) == INVALID and sp(fake, None, None, None) == INVALID
     for s in bad_settings:
         assert sp(fake, C.byref(s), None, None) == INVALID and sp(fake, C.byref(s), p(d), fake) == INVALID
 
     ro = L.pmpc_mpc_batch_rollout
-    ro.restype = C.c_int
-    ro.argtypes = [C.c_void_p, P_, C.c_int, C.c_double, C.c_int, C.POINTER(pa.SQPSettings), C.POINTER(pa.QPSettings), P_, P_, P_, C.c_void_p]
     ss, qs = pa.sqp_settings_default(), pa.qp_settings_sqp_default()
     xs = (C.c_double * 64)(*([MARK] * 64)); us = (C.c_double * 64)(*([MARK] * 64))
     ok = dict(h=fake, x0=p(u0), K=2, dt=0.05, shift=0, ss=C.byref(ss), qs=C.byref(qs), w=None, xs=p(xs), us=p(us), info=None)
@@ -194,45 +187,16 @@ def test_argument_validation_without_a_device(pa):
     assert all(v == MARK for v in xs) and all(v == MARK for v in us) and untouched()
 
 
-def test_ctypes_signatures_match_the_header(pa, monkeypatch):
-    """Run every Python wrapper against a recording stand-in of the library and compare the argtypes it set with the header's parameter list."""
-    import re
-    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "polympc_amd.h")).read(), flags=re.S)
+def test_every_entry_point_is_reached_by_a_wrapper(pa, monkeypatch):
+    """Run every Python wrapper against a recording stand-in of the library: each entry point is called, with the header's number of arguments,
+    each of a kind its declared type accepts (the types themselves: test_capi_cpu.test_ctypes_signatures_match_the_header)."""
     names = [n for n in NEW if n != "pmpc_plant_settings_default"]
-    want = {}
-    for name in names:
-        m = re.search(r"pmpc_status\s+" + name + r"\s*\(([^;]*)\)\s*;", hdr)
-        assert m, f"{name} is not declared in include/polympc_amd.h"
-        want[name] = ["ptr" if "*" in q or q.split()[-2].endswith("_fn") else q.split()[-2] for q in (r.strip() for r in m.group(1).split(","))]
-    seen = {}
-
-    class Fn:
-        def __init__(self, name):
-            self.name, self.argtypes, self.restype = name, None, C.c_int
-
-        def __call__(self, *args):
-            seen[self.name] = (list(self.argtypes), len(args))
-            return 0
-
-    class Lib:
-        def __init__(self, real):
-            self._real, self._fns = real, {}
-
-        def __getattr__(self, name):
-            if name in names or name in ("pmpc_mpc_batch_create", "pmpc_mpc_batch_create_user", "pmpc_mpc_batch_destroy"):
-                return self._fns.setdefault(name, Fn(name))
-            return getattr(self._real, name)
-
     subprocess.check_call(["make", "-C", CPP, "-s"])
     user = pa.UserOCP(os.path.join(CPP, "libuser_ocp.so"), "UserRobot")
-    monkeypatch.setattr(pa.capi, "lib", lambda fake=Lib(pa.lib()): fake)
-
-    class T:   # stands in for a torch CUDA tensor
-        is_cuda, is_contiguous = True, staticmethod(lambda: True)
-        data_ptr = staticmethod(lambda: 64)
-
+    fake = abi_header.RecordingLib(pa, names + ["pmpc_mpc_batch_create", "pmpc_mpc_batch_create_user", "pmpc_mpc_batch_destroy"])
+    monkeypatch.setattr(pa.capi, "lib", lambda: fake)
     ctx = pa.Context.__new__(pa.Context); ctx._ctx = C.c_void_p(8)
-    t = T()
+    t = abi_header.FakeTensor()
     ctx.plant_step_batch(0, 6, 1, 0.0, 2.0, 0.05, [[0.0] * 3], u0=[[0.0] * 2], d=[[2.0]])
     ctx.plant_step_batch_dev(0, 6, 1, 0.0, 2.0, 1, 0.05, t, u0=t, iterate=t, d=t, w=t)
     user.plant_step_batch(ctx, 6, 1, 0.0, 2.0, 0.05, [[0.0] * 3], u0=[[0.0] * 2], d=[[2.0]])
@@ -244,19 +208,9 @@ def test_ctypes_signatures_match_the_header(pa, monkeypatch):
         assert xs.shape == (1, 3, 3) and us.shape == (1, 2, 2) and info.shape == (1, 2)
         b._batch = C.c_void_p()
     ctx._ctx = C.c_void_p()   # (nothing to destroy)
-
-    def kind(ct):
-        if ct is C.c_int:
-            return "int"
-        if ct is C.c_double:
-            return "double"
-        assert ct is C.c_void_p or issubclass(ct, C._Pointer), ct
-        return "ptr"
     for name in names:
-        assert name in seen, f"no Python wrapper called {name}"
-        argtypes, nargs = seen[name]
-        assert [kind(a) for a in argtypes] == want[name], name
-        assert nargs == len(want[name]), name
+        assert name in fake.calls, f"no Python wrapper called {name}"
+        assert fake.calls[name] == len(abi_header.declarations()[name][1]), name
 
 
 def test_batch_mpc_rollout_builds_and_refuses_to_run_without_gpu():

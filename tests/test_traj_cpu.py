@@ -11,6 +11,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import abi_header  # noqa: E402
 import traj_ref  # noqa: E402
 
 NEW = ("pmpc_traj_sample_batch", "pmpc_traj_sample_batch_dev", "pmpc_traj_shift_batch_dev", "pmpc_traj_regrid_batch", "pmpc_traj_regrid_batch_dev",
@@ -36,41 +37,13 @@ def test_new_entry_points_exist_without_an_abi_bump(pa):
     assert hasattr(pa.capi.MPCBatch, "sample") and hasattr(pa.capi.MPCBatch, "shift")
 
 
-def test_ctypes_signatures_match_the_header(pa, monkeypatch):
-    """Run every Python wrapper against a recording stand-in of the library and compare the argtypes it set with the header's parameter list."""
-    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "polympc_amd.h")).read(), flags=re.S)
-    want = {}
-    for name in NEW:
-        m = re.search(r"pmpc_status\s+" + name + r"\s*\(([^;]*)\)\s*;", hdr)
-        assert m, f"{name} is not declared in include/polympc_amd.h"
-        want[name] = ["ptr" if "*" in p else p.split()[-2] for p in (q.strip() for q in m.group(1).split(","))]
-    seen = {}
-
-    class Fn:
-        def __init__(self, name):
-            self.name, self.argtypes, self.restype = name, None, C.c_int
-
-        def __call__(self, *args):
-            seen[self.name] = (list(self.argtypes), len(args))
-            return 0
-
-    class Lib:
-        def __init__(self, real):
-            self._real, self._fns = real, {}
-
-        def __getattr__(self, name):
-            if name in NEW or name in ("pmpc_mpc_batch_create", "pmpc_mpc_batch_destroy"):
-                return self._fns.setdefault(name, Fn(name))
-            return getattr(self._real, name)
-
-    monkeypatch.setattr(pa.capi, "lib", lambda fake=Lib(pa.lib()): fake)
-
-    class T:   # stands in for a torch CUDA tensor
-        is_cuda, is_contiguous = True, staticmethod(lambda: True)
-        data_ptr = staticmethod(lambda: 64)
-
+def test_every_entry_point_is_reached_by_a_wrapper(pa, monkeypatch):
+    """Run every Python wrapper against a recording stand-in of the library: each entry point is called, with the header's number of arguments,
+    each of a kind its declared type accepts (the types themselves: test_capi_cpu.test_ctypes_signatures_match_the_header)."""
+    fake = abi_header.RecordingLib(pa, NEW + ("pmpc_mpc_batch_create", "pmpc_mpc_batch_destroy"))
+    monkeypatch.setattr(pa.capi, "lib", lambda: fake)
     ctx = pa.Context.__new__(pa.Context); ctx._ctx = C.c_void_p(8)
-    t = T()
+    t = abi_header.FakeTensor()
     ctx.traj_sample_batch(3, 2, 0, 6, 1, 0.0, 2.0, [[0.0] * 35], [0.5])
     ctx.traj_sample_batch_dev(1, 3, 2, 0, 6, 1, 0.0, 2.0, t, 1, t, False, xs=t, us=t)
     ctx.traj_shift_batch_dev(1, 3, 2, 0, 0, 6, 1, 0.0, 2.0, 0.1, t, lam=t)
@@ -81,19 +54,9 @@ def test_ctypes_signatures_match_the_header(pa, monkeypatch):
     b.shift(0.1, duals=True)
     b._batch = C.c_void_p()
     ctx._ctx = C.c_void_p()   # (nothing to destroy)
-
-    def kind(ct):
-        if ct is C.c_int:
-            return "int"
-        if ct is C.c_double:
-            return "double"
-        assert ct is C.c_void_p or issubclass(ct, C._Pointer), ct
-        return "ptr"
     for name in NEW:
-        assert name in seen, f"no Python wrapper called {name}"
-        argtypes, nargs = seen[name]
-        assert [kind(a) for a in argtypes] == want[name], name
-        assert nargs == len(want[name]), name
+        assert name in fake.calls, f"no Python wrapper called {name}"
+        assert fake.calls[name] == len(abi_header.declarations()[name][1]), name
 
 
 def test_argument_validation_without_a_device(pa):
@@ -111,8 +74,6 @@ def test_argument_validation_without_a_device(pa):
 
     for name in ("pmpc_traj_sample_batch", "pmpc_traj_sample_batch_dev"):
         f = getattr(L, name)
-        f.restype = C.c_int
-        f.argtypes = [C.c_void_p] + [C.c_int] * 6 + [C.c_double] * 2 + [P_, C.c_int, P_, C.c_int, P_, P_]
         ok = dict(c=fake, B=1, nx=3, nu=2, np=0, P=6, S=1, t0=0.0, tf=2.0, x=p(xin), K=2, t=p(tin), tpi=0, xs=p(xs), us=p(us))
 
         def call(**kw):
@@ -131,8 +92,6 @@ def test_argument_validation_without_a_device(pa):
         assert untouched(), name
 
     sh = L.pmpc_traj_shift_batch_dev
-    sh.restype = C.c_int
-    sh.argtypes = [C.c_void_p] + [C.c_int] * 7 + [C.c_double] * 3 + [P_, P_]
     ok = dict(c=fake, B=1, nx=3, nu=2, np=0, ng=0, P=6, S=1, t0=0.0, tf=2.0, dt=0.1, x=p(xin), lam=p(xs))
 
     def shift(**kw):
@@ -149,8 +108,6 @@ def test_argument_validation_without_a_device(pa):
 
     for name in ("pmpc_traj_regrid_batch", "pmpc_traj_regrid_batch_dev"):
         f = getattr(L, name)
-        f.restype = C.c_int
-        f.argtypes = [C.c_void_p] + [C.c_int] * 8 + [C.c_double] * 2 + [P_, P_]
         ok = dict(c=fake, B=1, nx=3, nu=2, np=0, P=6, S=1, P2=5, S2=2, t0=0.0, tf=2.0, src=p(xin), dst=p(xs))
 
         def regrid(**kw):
@@ -165,11 +122,9 @@ def test_argument_validation_without_a_device(pa):
         assert untouched(), name
 
     bs = L.pmpc_mpc_batch_sample
-    bs.restype, bs.argtypes = C.c_int, [C.c_void_p, C.c_int, P_, C.c_int, P_, P_]
     assert bs(None, 1, p(tin), 0, p(xs), p(us)) == INVALID and bs(fake, 0, p(tin), 0, p(xs), p(us)) == INVALID
     assert bs(fake, 1, None, 0, p(xs), p(us)) == INVALID and bs(fake, 1, p(tin), 0, None, None) == INVALID and bs(fake, 1, p(tin), 2, p(xs), p(us)) == INVALID
     bh = L.pmpc_mpc_batch_shift
-    bh.restype, bh.argtypes = C.c_int, [C.c_void_p, C.c_double, C.c_int]
     assert bh(None, 0.1, 0) == INVALID and bh(fake, -0.1, 0) == INVALID and bh(fake, nan, 1) == INVALID and bh(fake, inf, 0) == INVALID
     assert untouched()
 
