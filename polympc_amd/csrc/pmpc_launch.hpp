@@ -1,6 +1,7 @@
 // polympc_amd — SQP / linearisation kernels and their launch templates. Included by pmpc_api.hip for the built-in OCPs
 // and by include/polympc/register_ocp.hpp for user-defined OCPs (compiled by hipcc in the user's translation unit).
-// Kernels: sqp_kernel<Model, NN, MM, V>, sqp_kernel_rr<Model, NN, MM, V>, sqp_schur_kernel<Model, P, S, V> — V the variant flags SQP_* of pmpc_sqp.hpp.
+// Kernels: sqp_kernel<Model, NN, MM, V>, sqp_kernel_modes<Model, NN, MM, V> (the register-resident sizes with their execution modes, SQP_MODES), sqp_kernel_rr<Model, NN, MM, V>,
+// sqp_schur_kernel<Model, P, S, V> — V the variant flags SQP_* of pmpc_sqp.hpp.
 // Launcher: sqp_launch_dev checks the request, then plan_schur → plan_reg (plan_extra_grids) → plan_generic fill one SqpPlan (kernel, LDS, redo step, route)
 // and launch_sqp_plan launches it.
 #pragma once
@@ -72,7 +73,6 @@ template <class Model> __host__ __device__ inline size_t big_scratch_doubles(int
 // KHBM: large-instance mode of the LDS-resident kernels — the KKT factor lives in an HBM workspace (Kws). A compile-time flag so
 // that in the normal mode every QP pointer provably addresses LDS (ds_read / ds_write instead of flat accesses, which cost the
 // LDS path most of its time when the location of K was a run-time choice)
-template <class Model, int NN = 0, int MM = 0, unsigned V = 0>   // V: the variant flags SQP_* (pmpc_sqp.hpp)
 #ifndef PMPC_SQP_WAVES
 #define PMPC_SQP_WAVES 2
 #endif
@@ -82,20 +82,30 @@ template <class Model, int NN = 0, int MM = 0, unsigned V = 0>   // V: the varia
 #ifndef PMPC_COND1_WAVES
 #define PMPC_COND1_WAVES 1   /* condensed register kernel on at most 64 variables: wavefronts per SIMD — measured on the 11-node robot grid: two wavefronts (256 registers: 240 spilled values, eight scratch accesses in the ADMM loop) 2.82 ms per 4096, one wavefront 2.67 (the full inverse: 4.04) */
 #endif
-__global__ __launch_bounds__((V & SQP_TEAM4) ? 256 : 64, ((NN > 0 && NN + MM <= 64) ? PMPC_SQP_WAVES : ((NN > 0 && (V & SQP_COND) && NN <= 64) ? PMPC_COND1_WAVES : (((V & SQP_HBM) && (V & SQP_TWO_WAVES)) ? 2 : ((V & SQP_HBM) ? PMPC_BIG_WAVES : 1))))) void sqp_kernel(Model model, const ChebData* __restrict__ cd, int B,
+// wavefronts per SIMD the launch bounds of sqp_kernel / sqp_kernel_modes<Model, NN, MM, V> ask for
+template <int NN, int MM, unsigned V> constexpr int sqp_kernel_waves() {
+    return (NN > 0 && NN + MM <= 64) ? PMPC_SQP_WAVES : ((NN > 0 && (V & SQP_COND) && NN <= 64) ? PMPC_COND1_WAVES : (((V & SQP_HBM) && (V & SQP_TWO_WAVES)) ? 2 : ((V & SQP_HBM) ? PMPC_BIG_WAVES : 1)));
+}
+// The body of the fused SQP kernel. V: the variant flags SQP_* (pmpc_sqp.hpp) — with SQP_MODES among them for sqp_kernel_modes. A register-resident body without the
+// execution modes (!sqp_has_modes<NN, V>()) is ONE whole solve from the guesses: it_begin, it_end and slice_state are not read (launch_sqp_plan passes 0, max_iter and
+// a pointer nobody follows), and ss.iteration_trace is ignored — plan_reg selects the build with the modes for every request that needs one of them.
+template <class Model, int NN, int MM, unsigned V>
+__device__ __forceinline__ void sqp_kernel_body(const Model& model, const ChebData* __restrict__ cd, int B,
                                                  const double* __restrict__ x_guess, const double* __restrict__ lam_guess,
                                                  const double* __restrict__ d, const double* __restrict__ lbx,
                                                  const double* __restrict__ ubx, const double* __restrict__ lbg,
-                                                 const double* __restrict__ ubg, pmpc_sqp_settings ss, pmpc_qp_settings qs,
+                                                 const double* __restrict__ ubg, const pmpc_sqp_settings& ss, const pmpc_qp_settings& qs,
                                                  double* __restrict__ Hws, double* __restrict__ Aws, double* __restrict__ x,
                                                  double* __restrict__ lam, pmpc_sqp_info* __restrict__ info, unsigned long long* __restrict__ phase_cycles,
                                                  double* __restrict__ Kws, int it_begin, int it_end, double* __restrict__ slice_state, unsigned lds_dyn_doubles) {
     static_assert(sqp_variant_ok<NN, V>(), "sqp_kernel: variant flags that no launcher route selects");
     constexpr bool PROF = (V & SQP_PROF) != 0, KHBM = (V & SQP_HBM) != 0, POL = (V & SQP_HOOKS) != 0, CND = (V & SQP_COND) != 0, WG4 = (V & SQP_TEAM4) != 0;
+    constexpr bool MODES = sqp_has_modes<NN, V>();
     extern __shared__ double smem[];
     const size_t lds_doubles_total = __builtin_amdgcn_groupstaticsize() / sizeof(double) + lds_dyn_doubles;
     const int b = blockIdx.x;
     if (b >= B) return;
+    if constexpr (!MODES) { it_begin = 0; it_end = 0; slice_state = nullptr; }   // one whole solve: every test of the three below folds away, the arguments are dead
     // redo launch (the full-KKT-form kernel behind a condensed one): only the instances whose condensed solve gave up at its conditioning gate
     int flags0 = 0;   // (redo launch: PMPC_FLAG_ILLCOND is part of the instance's flags from the start — information for the caller: this instance took the full KKT form)
     if (it_begin == PMPC_REDO_MODE) { if (__builtin_amdgcn_readfirstlane(info[b].status) != PMPC_SQP_REDO) return; it_begin = 0; flags0 = PMPC_FLAG_ILLCOND; }
@@ -224,7 +234,7 @@ __global__ __launch_bounds__((V & SQP_TEAM4) ? 256 : 64, ((NN > 0 && NN + MM <= 
     sqp.big_mail = big_mail;
     sqp.filt = filt;
     sqp.eig = eigw;
-    sqp.trace = ss.iteration_trace ? ss.iteration_trace + (size_t)b * (size_t)ss.iteration_trace_capacity * PMPC_TRACE_DOUBLES : nullptr;
+    if constexpr (MODES) sqp.trace = ss.iteration_trace ? ss.iteration_trace + (size_t)b * (size_t)ss.iteration_trace_capacity * PMPC_TRACE_DOUBLES : nullptr;
     sqp.tr = ocp.s.fval;   // first per-node staging array: everything from here on is dead while the QP runs
     if constexpr (NN + MM > 112) sqp.tr += (ocp.s.fval - lds) & 1;   // (on a 16-byte boundary there: the 8 x 8 register path reads its LDS tiles in 16-byte units. Only there — a second, separately live pointer cost the 7-node kernel a spill inside its ADMM loop)
     {   // side-by-side line search: G candidates x (m constraint values + NN Lagrange values) + 3 scalars each, in the same region
@@ -253,6 +263,26 @@ __global__ __launch_bounds__((V & SQP_TEAM4) ? 256 : 64, ((NN > 0 && NN + MM <= 
         __syncthreads();
     }
 }
+// The two entry points over that body, one argument list. sqp_kernel<Model, NN, MM, V> is the build its name has always meant — for the register-resident sizes the
+// plain one; sqp_kernel_modes<Model, NN, MM, V> (NN > 0, V without SQP_PROF / SQP_HOOKS / SQP_COND) is the same size and variant WITH the execution modes (SQP_MODES).
+#define PMPC_SQP_KERNEL_PARAMS Model model, const ChebData* __restrict__ cd, int B, const double* __restrict__ x_guess, const double* __restrict__ lam_guess, \
+    const double* __restrict__ d, const double* __restrict__ lbx, const double* __restrict__ ubx, const double* __restrict__ lbg, const double* __restrict__ ubg, \
+    pmpc_sqp_settings ss, pmpc_qp_settings qs, double* __restrict__ Hws, double* __restrict__ Aws, double* __restrict__ x, double* __restrict__ lam, \
+    pmpc_sqp_info* __restrict__ info, unsigned long long* __restrict__ phase_cycles, double* __restrict__ Kws, int it_begin, int it_end, double* __restrict__ slice_state, \
+    unsigned lds_dyn_doubles
+#define PMPC_SQP_KERNEL_ARGS model, cd, B, x_guess, lam_guess, d, lbx, ubx, lbg, ubg, ss, qs, Hws, Aws, x, lam, info, phase_cycles, Kws, it_begin, it_end, slice_state, lds_dyn_doubles
+template <class Model, int NN = 0, int MM = 0, unsigned V = 0>
+__global__ __launch_bounds__((V & SQP_TEAM4) ? 256 : 64, (sqp_kernel_waves<NN, MM, V>())) void sqp_kernel(PMPC_SQP_KERNEL_PARAMS) {
+    static_assert(!(V & SQP_MODES), "sqp_kernel: the execution modes of a register-resident size are sqp_kernel_modes");
+    sqp_kernel_body<Model, NN, MM, V>(PMPC_SQP_KERNEL_ARGS);
+}
+template <class Model, int NN, int MM, unsigned V = 0>
+__global__ __launch_bounds__(64, (sqp_kernel_waves<NN, MM, V>())) void sqp_kernel_modes(PMPC_SQP_KERNEL_PARAMS) {
+    static_assert(NN > 0 && !sqp_has_modes<NN, V>(), "sqp_kernel_modes: a register-resident variant whose sqp_kernel does not carry the modes already");
+    sqp_kernel_body<Model, NN, MM, V | SQP_MODES>(PMPC_SQP_KERNEL_ARGS);
+}
+#undef PMPC_SQP_KERNEL_PARAMS
+#undef PMPC_SQP_KERNEL_ARGS
 // ---------------------------------------------------------------------------------------------------------------------------------------------
 // Block-structured specialisation (pmpc_qp_schur.hpp): the Hessian is block diagonal per node — the block BFGS every control test of the reference
 // selects (continuous_ocp.hpp:2304-2431) or exact Hessians, NG = 0, at most one parameter (arrow shape: a border row / column beside the blocks) — and lives with J's per-node blocks in LDS: no HBM workspace, the QP through
@@ -315,7 +345,7 @@ void sqp_schur_kernel(Model model, const ChebData* __restrict__ cd, int B, const
     }
     for (int i = ln; i < m + n; i += WAVE) v.lam[i] = lam_guess ? lam_guess[(size_t)b * (m + n) + i] : 0.0;
     wsync();
-    SqpDevice<Model, n, m, V | SQP_BLOCK_BFGS, PP * 256 + SS> sqp(ocp, v, qw, nullptr, nullptr, ss, qs);
+    SqpDevice<Model, n, m, V | SQP_BLOCK_BFGS | SQP_MODES, PP * 256 + SS> sqp(ocp, v, qw, nullptr, nullptr, ss, qs);
     sqp.filt = filt;
     sqp.hblk = hblk; sqp.hbrd = hbrd; sqp.qblk = qblk; sqp.xsc = xsc; sqp.dsc = dsc; sqp.dtab = dtab;
     schur_build_tables<Model, PP, SS>(ocp.s.D, dtab);
@@ -506,7 +536,7 @@ __global__ __launch_bounds__(64, PMPC_SQP_WAVES) void sqp_kernel_rr(Model model,
         int done_iters = pass;
         if (gave_up) { si.iter = 0; si.qp_solver_iter = 0; si.status = PMPC_SQP_REDO; si.flags = PMPC_FLAG_ILLCOND; si.primal_norm = 0.0; si.dual_norm = 0.0; si.max_violation = 0.0; si.cost = 0.0; }
         else {
-            SqpDevice<Model, NN, MM, V> sqp(ocp, v, qw, K0, K0 + n, ss, qs);
+            SqpDevice<Model, NN, MM, V | SQP_MODES> sqp(ocp, v, qw, K0, K0 + n, ss, qs);   // (one iteration per call, trace records: the execution modes)
             sqp.filt = nullptr;
             sqp.eig = nullptr;
             sqp.trace = ss.iteration_trace ? ss.iteration_trace + (size_t)b * (size_t)ss.iteration_trace_capacity * PMPC_TRACE_DOUBLES : nullptr;
@@ -663,6 +693,12 @@ template <class Model> using SqpKernel = decltype(&sqp_kernel<Model>);   // (eve
 // (the last one spelled out: naming an instantiation of sqp_schur_kernel would evaluate SchurDims, which exists only for the models that kernel serves)
 template <class Model> using SqpSchurKernel = void (*)(Model, const ChebData*, int, const double*, const double*, const double*, const double*, const double*, pmpc_sqp_settings,
                                                        pmpc_qp_settings, double*, double*, pmpc_sqp_info*, unsigned long long*);
+// the entry point of <NN, MM, V> for a request: `modes` — it needs an execution mode (SQP_MODES: iteration slices, the resume launch behind the round-robin kernel, the
+// redo entry, an iteration trace) — selects the build that carries them, which for the developer / hook builds is sqp_kernel itself
+template <class Model, int NN, int MM, unsigned V = 0> inline SqpKernel<Model> sqp_kernel_for(bool modes) {
+    if constexpr (sqp_has_modes<NN, V>()) return sqp_kernel<Model, NN, MM, V>;
+    else return modes ? sqp_kernel_modes<Model, NN, MM, V> : sqp_kernel<Model, NN, MM, V>;
+}
 template <class Model> struct SqpPlan {
     int route = PMPC_ROUTE_NONE;   // recorded for pmpc_sqp_last_route
     SqpKernel<Model> kern = nullptr;
@@ -778,27 +814,31 @@ inline bool plan_reg(pmpc_context* ctx, const SqpArgs<Model>& a, SqpPlan<Model>&
         if (ONE_ROW && LEAN && (ss->hessian_update == 1 || a.phase)) return false;
         // the full-inverse kernel
         p.route = ONE_ROW ? PMPC_ROUTE_REG1 : PMPC_ROUTE_REG2;
-        p.kern = sqp_kernel<Model, NN_, MM_>;
         p.lds = lds_full;
+        // execution modes (SQP_MODES): a plain request — one launch, the whole solve, no trace — takes the build without them; iteration slices, the resume launch behind
+        // the round-robin kernel and an iteration trace take the build that carries them
+        bool modes = a.slice_iters > 0 || ss->iteration_trace != nullptr;
+        if constexpr (ONE_ROW && !LEAN) {   // more instances than resident wavefronts: one SQP iteration per work item (PMPC_SQP_RR=1, sqp_kernel_rr)
+#ifdef PMPC_RR_PROFILE
+            const bool rr_phase_ok = true;
+#else
+            const bool rr_phase_ok = !a.phase;
+#endif
+            const int slots = PMPC_SQP_WAVES * pmpc_internal_simd_count(ctx);
+            if (!pol && a.slice_state && a.slice_iters == 0 && rr_phase_ok && ss->max_iter > 1 && ss->max_iter <= RR_MAX_ITER && a.B > slots && a.B <= RR_MAX_BATCH &&
+                (size_t)a.B * ss->max_iter < ((size_t)1 << 30) && pmpc_internal_sqp_rr(ctx)) {
+                p.rr = (ss->hessian_update == 1) ? sqp_kernel_rr<Model, NN_, MM_, SQP_BLOCK_BFGS> : sqp_kernel_rr<Model, NN_, MM_, 0>;
+                p.rr_init = sqp_rr_init_kernel<Model>;
+                modes = true;
+            }
+        }
+        p.kern = sqp_kernel_for<Model, NN_, MM_>(modes);
         if constexpr (ONE_ROW) {
             p.timed = true;
-            if constexpr (!LEAN)
-                p.kern = (ss->hessian_update == 1) ? sqp_kernel<Model, NN_, MM_, SQP_BLOCK_BFGS>   // (no phase timers in the block-BFGS specialisation)
-                                                   : (a.phase ? sqp_kernel<Model, NN_, MM_, SQP_PROF> : sqp_kernel<Model, NN_, MM_>);
+            if constexpr (!LEAN)   // the Hessian-update policy is a compile-time flag of the one-row-per-lane kernels (SQP_BLOCK_BFGS: no phase timers in that specialisation)
+                p.kern = (ss->hessian_update == 1) ? sqp_kernel_for<Model, NN_, MM_, SQP_BLOCK_BFGS>(modes)
+                                                   : (a.phase ? sqp_kernel<Model, NN_, MM_, SQP_PROF> : sqp_kernel_for<Model, NN_, MM_>(modes));
             plan_redo_lds(ctx, a, p);
-            if constexpr (!LEAN) {   // more instances than resident wavefronts: one SQP iteration per work item (PMPC_SQP_RR=1, sqp_kernel_rr)
-#ifdef PMPC_RR_PROFILE
-                const bool rr_phase_ok = true;
-#else
-                const bool rr_phase_ok = !a.phase;
-#endif
-                const int slots = PMPC_SQP_WAVES * pmpc_internal_simd_count(ctx);
-                if (!pol && a.slice_state && a.slice_iters == 0 && rr_phase_ok && ss->max_iter > 1 && ss->max_iter <= RR_MAX_ITER && a.B > slots && a.B <= RR_MAX_BATCH &&
-                    (size_t)a.B * ss->max_iter < ((size_t)1 << 30) && pmpc_internal_sqp_rr(ctx)) {
-                    p.rr = (ss->hessian_update == 1) ? sqp_kernel_rr<Model, NN_, MM_, SQP_BLOCK_BFGS> : sqp_kernel_rr<Model, NN_, MM_, 0>;
-                    p.rr_init = sqp_rr_init_kernel<Model>;
-                }
-            }
         } else if constexpr (LDS_PATH_PROFILED<Model>::value && !LEAN) {   // developer builds with phase timers
             if (a.phase && !pol) { p.kern = sqp_kernel<Model, NN_, MM_, SQP_PROF>; p.timed = true; }
         }
@@ -811,7 +851,7 @@ inline bool plan_reg(pmpc_context* ctx, const SqpArgs<Model>& a, SqpPlan<Model>&
 #if PMPC_EXPERIMENT_COND_SMALL   /* developer experiment (round 6, EXPERIMENTS.md): the CONDENSED register QP on a grid of at most 64 KKT rows — config A on 35 instead of 56 rows; the redo stays on the LDS-resident kernel */
         if constexpr (ONE_ROW && !LEAN && NNODES == 7 && Model::NP == 0 && Model::NG == 0) {
             if (!pol && condreg && ss->hessian_update == 0 && !a.phase) {
-                p.route = PMPC_ROUTE_CONDREG; p.kern = sqp_kernel<Model, NN_, MM_, SQP_COND>; p.rr = nullptr;
+                p.route = PMPC_ROUTE_CONDREG; p.kern = sqp_kernel_for<Model, NN_, MM_, SQP_COND>(a.slice_iters > 0 || ss->iteration_trace != nullptr); p.rr = nullptr;
                 p.lds = sqp_kernel_lds_bytes<Model>(a.P, a.S, SqpLdsLayout::Cond1);
             }
         }
@@ -822,9 +862,9 @@ inline bool plan_reg(pmpc_context* ctx, const SqpArgs<Model>& a, SqpPlan<Model>&
                 if constexpr (NN_ <= WAVE) lds = sqp_kernel_lds_bytes<Model>(a.P, a.S, SqpLdsLayout::Cond1);   // (two wavefronts per SIMD: a smaller staging lets more instances share a CU)
                 else lds = sqp_kernel_lds_bytes<Model>(a.P, a.S, SqpLdsLayout::Cond2, 0, false, (size_t)cond_qp_staging<NN_, MM_, NNODES>());   // (its own tile set's staging, not the full inverse's: four instead of three instances per CU on the 16-node grid)
                 bool timed = false;
-                auto kern = sqp_kernel<Model, NN_, MM_, SQP_COND>;
+                auto kern = sqp_kernel_for<Model, NN_, MM_, SQP_COND>(modes);
                 if constexpr (LDS_PATH_PROFILED<Model>::value && !LEAN) { if (a.phase) { kern = sqp_kernel<Model, NN_, MM_, SQP_PROF | SQP_COND>; timed = true; } }
-                condensed(kern, lds, timed, sqp_kernel<Model, NN_, MM_>);
+                condensed(kern, lds, timed, sqp_kernel_for<Model, NN_, MM_>(true));   // (the redo entry is an execution mode)
             }
         }
         // hook override: the builds with the policy hooks compiled in (POL)

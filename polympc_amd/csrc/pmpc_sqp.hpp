@@ -98,6 +98,16 @@ constexpr int PMPC_REDO_MODE = -0x7fffffff - 1;   // it_begin of that redo launc
 // SQP_TEAM4 (WG4): the HBM-factor kernel on a workgroup of FOUR wavefronts per instance (BigTeam, pmpc_qp_big.hpp: small batches / lone instances);
 //      with SQP_TWO_WAVES the team kernel built for 256 registers — two workgroups per CU, its register budget from the launch bound alone
 enum : unsigned { SQP_PROF = 1, SQP_BLOCK_BFGS = 2, SQP_HBM = 4, SQP_TWO_WAVES = 8, SQP_HOOKS = 16, SQP_COND = 32, SQP_TEAM4 = 64 };
+// SQP_MODES (a bit of the SqpDevice / kernel-body variant word above the flags that name an sqp_kernel<...> symbol): the EXECUTION MODES of a register-resident kernel (NN > 0) —
+//      iteration slices (it_begin / it_end, slice_state), the resume launch behind the round-robin kernel (it_begin < 0), the redo entry (PMPC_REDO_MODE) and the iteration
+//      trace. Without it a register-resident body is compiled for ONE whole solve from the guesses: it_begin == 0, it_end == max_iter, no slice_state, no trace stores — those
+//      kernel arguments are dead in it. The flag is carried by sqp_kernel_modes<Model, NN, MM, V> (pmpc_launch.hpp: a second entry point over the same body, so that
+//      sqp_kernel<Model, NN, MM, V> keeps naming the plain build), by sqp_kernel_rr and by the block-structured kernels. The size-generic kernels (NN == 0) and the developer /
+//      hook builds (SQP_PROF, SQP_HOOKS) always carry the modes (sqp_has_modes): no second instantiation of those. Nor of the condensed kernels (SQP_COND): built without
+//      the modes, two of them (robot, 9 and 11 nodes) came out with compiler hazard 3 of DESIGN.md — an accumulation register written inside a partial-EXEC block and read
+//      back at full EXEC, reported by tests/test_kernel_occupancy_cpu.py on the built library; with the modes, as they have always been built, they are clean.
+enum : unsigned { SQP_MODES = 128 };
+template <int NN, unsigned V> constexpr bool sqp_has_modes() { return NN == 0 || (V & (SQP_MODES | SQP_PROF | SQP_HOOKS | SQP_COND)) != 0; }
 // what every instantiation site of the launcher keeps to, checked at the kernel heads
 template <int NN, unsigned V> constexpr bool sqp_variant_ok() {
     return (!(V & SQP_HBM) || NN == 0) &&                              // the HBM-factor kernels are size-generic
@@ -106,7 +116,8 @@ template <int NN, unsigned V> constexpr bool sqp_variant_ok() {
            (!(V & SQP_COND) || NN > 0) &&                              // condensed QP, hook builds, compiled-in block BFGS: register-resident kernels
            (!(V & SQP_HOOKS) || NN > 0) &&                             // (size-generic kernels always carry the hooks)
            (!(V & SQP_BLOCK_BFGS) || NN > 0) &&
-           V < 2 * SQP_TEAM4;                                          // no unknown bits
+           (!(V & SQP_MODES) || NN > 0) &&                             // execution modes as a flag: register-resident kernels (the others always carry them)
+           (V & ~SQP_MODES) < 2 * SQP_TEAM4;                           // no unknown bits
 }
 // PS: P * 256 + S of a BLOCK-STRUCTURED specialisation (pmpc_qp_schur.hpp; 0 = none): the Hessian is block diagonal per node (block BFGS or exact
 //      Hessians, NG = 0; NP = 1: the arrow shape, `hbrd` holds the border row with the corner and the border column) and lives as per-node blocks in LDS (`hblk`), J as its per-node blocks (`ocp.jblk`) + the differentiation matrix: the
@@ -116,6 +127,7 @@ struct SqpDevice {
     static_assert(sqp_variant_ok<NN, VARIANT>() && PS >= 0, "SqpDevice: variant flags that no kernel is built with");
     static constexpr bool PROF = (VARIANT & SQP_PROF) != 0, BIG = (VARIANT & SQP_HBM) != 0, POL = (VARIANT & SQP_HOOKS) != 0;
     static constexpr int HU = (VARIANT & SQP_BLOCK_BFGS) ? 1 : 0;
+    static constexpr bool MODES = sqp_has_modes<NN, VARIANT>();   // iteration slices and the iteration trace (SQP_MODES); without: solve() runs iterations 1 .. max_iter and writes no trace
     static constexpr bool SCH = PS > 0;
     static constexpr bool SLIM = BIG && (VARIANT & SQP_TWO_WAVES) && !(VARIANT & SQP_TEAM4);   // large-instance mode compiled for two wavefronts per SIMD (256 registers; not the team kernel)
     static constexpr int BIG_NW = (BIG && (VARIANT & SQP_TEAM4)) ? 4 : 1;   // large-instance mode on a workgroup of four wavefronts (BigTeam, pmpc_qp_big.hpp): this object lives on the first one
@@ -1261,9 +1273,10 @@ struct SqpDevice {
     }
 
     // SQP iterations it_begin+1 .. min(it_end, max_iter). status PMPC_SQP_IN_PROGRESS (internal) when the slice ends first.
+    // (!MODES: iterations 1 .. max_iter — it_begin, it_end and the trace are not read)
     __device__ __forceinline__ void solve(pmpc_sqp_info& info, int it_begin, int it_end) {
         int status = PMPC_SQP_MAX_ITER_EXCEEDED;
-        int iter = it_begin;
+        int iter = MODES ? it_begin : 0;
         // single code site for the (large) QP + line-search body: first pass = exact linearisation (:583), later = update (:649)
         while (true) {
             ++iter;
@@ -1276,6 +1289,7 @@ struct SqpDevice {
             const bool done = __builtin_amdgcn_readfirstlane((int)termination_criteria()) != 0;
             const long long c3 = now();
             acc(0, c1 - c0); acc(3, c3 - c2); acc(4, c3 - c0); (void)c2;
+            if constexpr (MODES)
             if (trace != nullptr && iter <= ss.iteration_trace_capacity && lane_id() == 0) {   // what sqp_settings_t::iteration_callback could read (sqp_base.hpp:685-686)
                 double* r = trace + (size_t)(iter - 1) * PMPC_TRACE_DOUBLES;
                 r[0] = (double)iter; r[1] = alpha_log; r[2] = primal_norm; r[3] = dual_norm; r[4] = cost_log;
@@ -1287,7 +1301,7 @@ struct SqpDevice {
             }
             if (done) { status = PMPC_SQP_SOLVED; break; }
             if (iter >= ss.max_iter) break;
-            if (iter >= it_end) { status = PMPC_SQP_IN_PROGRESS; break; }
+            if constexpr (MODES) { if (iter >= it_end) { status = PMPC_SQP_IN_PROGRESS; break; } }
         }
         {   // a non-finite iterate is reported whatever produced it (a QP solution, a diverging step of a warm start from an unconverged point, the model itself)
             bool bad = false;
