@@ -1,6 +1,7 @@
 """The IEEE-only sin / cos / exp shared by the HIP kernels and the CPU restatement (polympc_amd/csrc/pmpc_math.hpp), pinned to glibc —
-the functions the reference binary calls — and to exact values. CPU only (the device side of the same header is covered by the
-bit-for-bit GPU parity tests)."""
+the functions the reference binary calls — and to exact values. CPU only. The device side of the same header is held to its host side
+bit for bit by tests/test_gpu_ad_probe.py, on these ranges and on the arguments no model produces (every step of rem_pio2, the 2^50 cut-off,
+subnormal exp results, the exp clamps, zeros, infinities, NaN); the host side is held to mpmath by tests/test_ad_probe_cpu.py."""
 import numpy as np
 import pytest
 
