@@ -42,13 +42,13 @@ template <int NKKT> constexpr int reg_qp_staging() {
 }
 
 // the same for the CONDENSED register QP (pmpc_qp_cond.hpp) of NN variables, MM rows on NNODES nodes: its tile set's staging (the one-row-per-lane set up to 64
-// variables; beyond, RegKkt2<NN, PMPC_COND_NV> — NOT the (NN + MM)-row full inverse's, whose LDS-resident operand tiles the condensed kernel does not have) or
+// variables; beyond, RegKkt2<NN, COND_NV> — NOT the (NN + MM)-row full inverse's, whose LDS-resident operand tiles the condensed kernel does not have) or
 // the exchange vectors + D~ tables that alias it, whichever is larger. (Until round 5 the condensed kernels were launched with the full inverse's staging: the
 // 16-node robot grid took 53.7 KB per instance — THREE workgroups per CU, a SIMD idle — where 33.6 KB do.)
 template <int NN, int MM, int NNODES> constexpr int cond_qp_staging() {
     if constexpr (NN <= WAVE) return RegKkt<NN>::TRI;
     else {
-        constexpr int a = RegKkt2<NN, PMPC_COND_NV>::TRI, b = CondDims<NN, MM>::TAB_OFF + CondDims<NN, MM>::template tab_doubles<NNODES>();
+        constexpr int a = RegKkt2<NN, COND_NV>::TRI, b = CondDims<NN, MM>::TAB_OFF + CondDims<NN, MM>::template tab_doubles<NNODES>();
         return a > b ? a : b;
     }
 }
@@ -73,18 +73,12 @@ template <class Model> __host__ __device__ inline size_t big_scratch_doubles(int
 // KHBM: large-instance mode of the LDS-resident kernels — the KKT factor lives in an HBM workspace (Kws). A compile-time flag so
 // that in the normal mode every QP pointer provably addresses LDS (ds_read / ds_write instead of flat accesses, which cost the
 // LDS path most of its time when the location of K was a run-time choice)
-#ifndef PMPC_SQP_WAVES
-#define PMPC_SQP_WAVES 2
-#endif
-#ifndef PMPC_BIG_WAVES
-#define PMPC_BIG_WAVES 1
-#endif
-#ifndef PMPC_COND1_WAVES
-#define PMPC_COND1_WAVES 1   /* condensed register kernel on at most 64 variables: wavefronts per SIMD — measured on the 11-node robot grid: two wavefronts (256 registers: 240 spilled values, eight scratch accesses in the ADMM loop) 2.82 ms per 4096, one wavefront 2.67 (the full inverse: 4.04) */
-#endif
+constexpr int SQP_WAVES = 2;
+constexpr int BIG_WAVES = 1;
+constexpr int COND1_WAVES = 1;   // condensed register kernel on at most 64 variables: wavefronts per SIMD — measured on the 11-node robot grid: two wavefronts (256 registers: 240 spilled values, eight scratch accesses in the ADMM loop) 2.82 ms per 4096, one wavefront 2.67 (the full inverse: 4.04)
 // wavefronts per SIMD the launch bounds of sqp_kernel / sqp_kernel_modes<Model, NN, MM, V> ask for
 template <int NN, int MM, unsigned V> constexpr int sqp_kernel_waves() {
-    return (NN > 0 && NN + MM <= 64) ? PMPC_SQP_WAVES : ((NN > 0 && (V & SQP_COND) && NN <= 64) ? PMPC_COND1_WAVES : (((V & SQP_HBM) && (V & SQP_TWO_WAVES)) ? 2 : ((V & SQP_HBM) ? PMPC_BIG_WAVES : 1)));
+    return (NN > 0 && NN + MM <= 64) ? SQP_WAVES : ((NN > 0 && (V & SQP_COND) && NN <= 64) ? COND1_WAVES : (((V & SQP_HBM) && (V & SQP_TWO_WAVES)) ? 2 : ((V & SQP_HBM) ? BIG_WAVES : 1)));
 }
 // The body of the fused SQP kernel. V: the variant flags SQP_* (pmpc_sqp.hpp) — with SQP_MODES among them for sqp_kernel_modes. A register-resident body without the
 // execution modes (!sqp_has_modes<NN, V>()) is ONE whole solve from the guesses: it_begin, it_end and slice_state are not read (launch_sqp_plan passes 0, max_iter and
@@ -114,7 +108,7 @@ __device__ __forceinline__ void sqp_kernel_body(const Model& model, const ChebDa
     // it_begin < 0: resume mode (the launch behind the round-robin kernel, sqp_kernel_rr below): every instance continues from the iteration its own record holds
     if (it_begin < 0) it_begin = __builtin_amdgcn_readfirstlane(info[b].iter);
     const int P = cd->P, S = cd->S;
-    // register-resident instantiations (NN > 0): the node count, and with it n, m, mi and the LDS carve below, are constants of this body (PMPC_STATIC_LAYOUT, pmpc_ocp.hpp).
+    // register-resident instantiations (NN > 0): the node count, and with it n, m, mi and the LDS carve below, are constants of this body (static layout, pmpc_ocp.hpp).
     // Valid because plan_reg launches <NN, MM> only where a.P * a.S + 1 == NNODES; P and S themselves stay run-time values
     constexpr int KN = static_nodes<Model, NN, MM>();
     constexpr bool ROLLED = KN > 0;   // the cold loops below keep a run-time bound (rolled_bound)
@@ -243,7 +237,7 @@ __device__ __forceinline__ void sqp_kernel_body(const Model& model, const ChebDa
         const size_t have = (size_t)(stage_end - ocp.s.fval);   // the staging block only — never the parameters / filter carved behind it
         sqp.lsbuf = ocp.s.fval;   // a flag, not a null pointer, says whether it fits (compiler hazard 7: null tests of LDS pointers)
         sqp.ls_side_by_side = (G >= 2 && need <= have);
-        sqp.ls_wide = sqp.ls_side_by_side && need + (size_t)2 * G * n <= have;   // the box-term pairs of the G candidates behind them (PMPC_WIDE_TERMS >= 2; without room the summing lanes form the terms)
+        sqp.ls_wide = sqp.ls_side_by_side && need + (size_t)2 * G * n <= have;   // the box-term pairs of the G candidates behind them (wide terms; without room the summing lanes form the terms)
     }
     pmpc_sqp_info si;
     sqp.qp_flags = flags0;
@@ -300,7 +294,7 @@ template <class Model, int PP, int SS> inline size_t sqp_schur_lds_bytes(bool po
     return ((size_t)(2 * dm.n + dm.m) + SqpLds::doubles(dm.n, dm.m, dm.mi) + stage + schur_lds_doubles_ct<Model, PP, SS>() + (Model::ND > 0 ? Model::ND : 1) + (pol ? FILTER_LDS_DOUBLES : 0) + 2) * sizeof(double);
 }
 template <class Model, int PP, int SS, unsigned V = 0>   // V: SQP_PROF, SQP_HOOKS (POL: with the filter line search, line_search = 1, LSFilter carried in LDS — the hook of the reference's tests this kernel family carries)
-__global__ __launch_bounds__(64, (SchurDims<Model, PP, SS>::N + SchurDims<Model, PP, SS>::M <= 64) ? PMPC_SQP_WAVES : 1)
+__global__ __launch_bounds__(64, (SchurDims<Model, PP, SS>::N + SchurDims<Model, PP, SS>::M <= 64) ? SQP_WAVES : 1)
 void sqp_schur_kernel(Model model, const ChebData* __restrict__ cd, int B, const double* __restrict__ x_guess, const double* __restrict__ lam_guess,
                       const double* __restrict__ d, const double* __restrict__ lbx, const double* __restrict__ ubx, pmpc_sqp_settings ss,
                       pmpc_qp_settings qs, double* __restrict__ x, double* __restrict__ lam, pmpc_sqp_info* __restrict__ info,
@@ -416,10 +410,7 @@ constexpr int RR_PASS_SHIFT = 24;                            // entry = (b + 1) 
 constexpr int RR_MAX_BATCH = (1 << RR_PASS_SHIFT) - 2;
 constexpr int RR_MAX_ITER = 127;
 constexpr int RR_SPIN_LIMIT = 1 << 16;
-#ifndef PMPC_RR_HARD_TENTHS
-#define PMPC_RR_HARD_TENTHS 14
-#endif
-constexpr int RR_HARD_TENTHS = PMPC_RR_HARD_TENTHS;   // an iteration is 'hard' when it takes more than this many tenths of the wavefront's mean
+constexpr int RR_HARD_TENTHS = 14;   // an iteration is 'hard' when it takes more than this many tenths of the wavefront's mean
 inline size_t rr_queue_bytes(int B, int max_iter) { return ((size_t)RR_HEADER_WORDS + (size_t)B * (size_t)(max_iter > 0 ? max_iter : 1)) * sizeof(int); }
 __host__ __device__ inline int rr_queue_len(int B, int q) { return (q < B) ? (B - q + RR_QUEUES - 1) / RR_QUEUES : 0; }   // instances q, q + 8, ...
 
@@ -443,13 +434,13 @@ __global__ __launch_bounds__(256) void sqp_rr_init_kernel(int* __restrict__ queu
 }
 
 template <class Model, int NN, int MM, unsigned V>   // V: SQP_BLOCK_BFGS or nothing
-__global__ __launch_bounds__(64, PMPC_SQP_WAVES) void sqp_kernel_rr(Model model, const ChebData* __restrict__ cd, int B,
+__global__ __launch_bounds__(64, SQP_WAVES) void sqp_kernel_rr(Model model, const ChebData* __restrict__ cd, int B,
                                                  const double* __restrict__ x_guess, const double* __restrict__ lam_guess,
                                                  const double* __restrict__ d, const double* __restrict__ lbx,
                                                  const double* __restrict__ ubx, const double* __restrict__ lbg,
                                                  const double* __restrict__ ubg, pmpc_sqp_settings ss, pmpc_qp_settings qs,
                                                  double* __restrict__ Hws, double* __restrict__ x, double* __restrict__ lam, pmpc_sqp_info* __restrict__ info,
-                                                 double* __restrict__ slice_state, int* __restrict__ queue, unsigned lds_dyn_doubles, unsigned long long* __restrict__ prof) {
+                                                 double* __restrict__ slice_state, int* __restrict__ queue, unsigned lds_dyn_doubles) {
     static_assert(NN > 0 && NN + MM <= WAVE && (V & ~SQP_BLOCK_BFGS) == 0, "round-robin execution exists for the one-row-per-lane register path, default hooks");
     extern __shared__ double smem[];
     const int P = cd->P, S = cd->S;
@@ -483,34 +474,21 @@ __global__ __launch_bounds__(64, PMPC_SQP_WAVES) void sqp_kernel_rr(Model model,
     int* entries = queue + RR_HEADER_WORDS + start;
     const int G = WAVE / ocp.dm.NN;
     const bool side_by_side = (G >= 2 && (size_t)G * (m + ocp.dm.NN + 3) <= (size_t)(stage_end - ocp.s.fval));
-#ifdef PMPC_RR_PROFILE   // developer build: cycles per wavefront in [0] whole life [1] solve [2] waiting for an entry [3] state load [4] state store + push; [5] work items [6] wavefronts
-    long long pc[5] = {0, 0, 0, 0, 0}; int items = 0; const long long life0 = clock64();
-#define RR_EXIT do { if (prof && ln == 0) { atomicAdd(&prof[0], (unsigned long long)(clock64() - life0)); for (int i_ = 1; i_ < 5; ++i_) atomicAdd(&prof[i_], (unsigned long long)pc[i_]); atomicAdd(&prof[5], (unsigned long long)items); atomicAdd(&prof[6], 1ull); } return; } while (0)
-#define RR_T(var) const long long var = clock64()
-#define RR_ACC(i, a, b) pc[i] += (b) - (a)
-#else
-#define RR_EXIT return
-#define RR_T(var)
-#define RR_ACC(i, a, b)
-    (void)prof;
-#endif
     long long cyc_sum = 0; int cyc_items = 0;   // this wavefront's iterations so far (shader-clock cycles)
     while (true) {
-        RR_T(t0);
         int hq = 0;
         if (ln == 0) hq = __hip_atomic_fetch_add(head, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         hq = __builtin_amdgcn_readfirstlane(hq);
-        if (hq >= cap) RR_EXIT;   // beyond every push the queue can ever see
+        if (hq >= cap) return;   // beyond every push the queue can ever see
         int e = __builtin_amdgcn_readfirstlane(__hip_atomic_load(&entries[hq], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
         for (int spin = 0; e == 0; ++spin) {
-            if (spin >= RR_SPIN_LIMIT) RR_EXIT;   // (the resume-mode launch finishes what is left)
-            if (__builtin_amdgcn_readfirstlane(__hip_atomic_load(finished, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) >= nk) RR_EXIT;
+            if (spin >= RR_SPIN_LIMIT) return;   // (the resume-mode launch finishes what is left)
+            if (__builtin_amdgcn_readfirstlane(__hip_atomic_load(finished, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) >= nk) return;
             __builtin_amdgcn_s_sleep(8);
             e = __builtin_amdgcn_readfirstlane(__hip_atomic_load(&entries[hq], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
         }
         const int b = (e & ((1 << RR_PASS_SHIFT) - 1)) - 1;
         const int pass = (int)((unsigned)e >> RR_PASS_SHIFT);   // SQP iterations the instance has behind it
-        RR_T(t1);
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
         for (int i = ln; i < Model::ND; i += WAVE) dL[i] = d[(size_t)b * Model::ND + i];
         double* sst = slice_state + (size_t)b * 2 * n;   // [previous Lagrangian gradient | previous step]
@@ -530,7 +508,6 @@ __global__ __launch_bounds__(64, PMPC_SQP_WAVES) void sqp_kernel_rr(Model model,
             v.ubg[i] = ubg ? ubg[(size_t)b * mi + i] : INFINITY;
         }
         wsync();
-        RR_T(t2);
         double* K0 = Hws + (size_t)b * (size_t)(n + m) * n;
         pmpc_sqp_info si;
         int done_iters = pass;
@@ -557,13 +534,6 @@ __global__ __launch_bounds__(64, PMPC_SQP_WAVES) void sqp_kernel_rr(Model model,
                 if (!hard) break;
             }
         }
-        RR_T(t3);
-#ifdef PMPC_RR_PROFILE   // per-item wall-clock stamps (100 MHz) in the alpha / primal_norm / dual_norm fields of the iteration record
-        if (ss.iteration_trace && ln == 0 && si.iter <= ss.iteration_trace_capacity) {
-            double* r_ = ss.iteration_trace + ((size_t)b * (size_t)ss.iteration_trace_capacity + (size_t)(si.iter - 1)) * PMPC_TRACE_DOUBLES;
-            r_[1] = (double)wall_clock64(); r_[2] = (double)(t2 - t0); r_[3] = (double)(t3 - t2); r_[4] = (double)xcc;
-        }
-#endif
         const bool more = si.status == PMPC_SQP_IN_PROGRESS;
         int tq = 0;
         if (more && ln == 0) tq = __hip_atomic_fetch_add(tail, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // (reserved while the stores below are in flight)
@@ -577,13 +547,7 @@ __global__ __launch_bounds__(64, PMPC_SQP_WAVES) void sqp_kernel_rr(Model model,
             else __hip_atomic_fetch_add(finished, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
         wsync();
-#ifdef PMPC_RR_PROFILE
-        { const long long t4 = clock64(); RR_ACC(2, t0, t1); RR_ACC(3, t1, t2); RR_ACC(1, t2, t3); RR_ACC(4, t3, t4); ++items; }
-#endif
     }
-#undef RR_EXIT
-#undef RR_T
-#undef RR_ACC
 }
 template <class Model> inline size_t sqp_eig_lds_bytes(int P, int S, const pmpc_sqp_settings* ss) {   // regularisation = 1: Jacobi workspace
     OcpDims<Model> dm(P, S);
@@ -685,9 +649,6 @@ template <> struct LDS_PATH_PROFILED<RobotOCP> { static constexpr bool value = t
 template <> struct LDS_PATH_PROFILED<CstrOCP> { static constexpr bool value = true; };
 template <> struct LDS_PATH_PROFILED<KiteStandInOCP> { static constexpr bool value = true; };
 
-#ifndef PMPC_EXPERIMENT_COND_SMALL
-#define PMPC_EXPERIMENT_COND_SMALL 0
-#endif
 // Launch plan of the fused SQP kernel: the route a selection function (plan_schur, plan_reg, plan_generic) decided on, launched by launch_sqp_plan
 template <class Model> using SqpKernel = decltype(&sqp_kernel<Model>);   // (every instantiation of sqp_kernel shares one function type, and so do those of sqp_kernel_rr and of sqp_schur_kernel)
 // (the last one spelled out: naming an instantiation of sqp_schur_kernel would evaluate SchurDims, which exists only for the models that kernel serves)
@@ -741,8 +702,8 @@ template <class Model> inline pmpc_status launch_sqp_plan(pmpc_context* ctx, con
         int* queue = (int*)(a.slice_state + (size_t)a.B * 2 * OcpDims<Model>(a.P, a.S).n);   // behind the slice state (sqp_launch_dev sizes the workspace for it)
         const size_t words = (size_t)a.B * ss.max_iter > (size_t)RR_HEADER_WORDS ? (size_t)a.B * ss.max_iter : (size_t)RR_HEADER_WORDS;
         hipLaunchKernelGGL(p.rr_init, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, a.stream, queue, a.info, a.B, ss.max_iter);
-        hipLaunchKernelGGL(p.rr, dim3(PMPC_SQP_WAVES * pmpc_internal_simd_count(ctx)), dim3(WAVE), p.lds, a.stream, a.mdl, a.cd, a.B, a.x_guess, a.lam_guess, a.d,
-                           a.lbx, a.ubx, a.lbg, a.ubg, ss, *a.qs, a.Hws, a.x, a.lam, a.info, a.slice_state, queue, (unsigned)(p.lds / sizeof(double)), phase);
+        hipLaunchKernelGGL(p.rr, dim3(SQP_WAVES * pmpc_internal_simd_count(ctx)), dim3(WAVE), p.lds, a.stream, a.mdl, a.cd, a.B, a.x_guess, a.lam_guess, a.d,
+                           a.lbx, a.ubx, a.lbg, a.ubg, ss, *a.qs, a.Hws, a.x, a.lam, a.info, a.slice_state, queue, (unsigned)(p.lds / sizeof(double)));
         launch_sqp_kernel(p.kern, a, p.threads, p.lds, ss, phase, p.Kws, -1, ss.max_iter, a.slice_state);
     } else {
         const int slice = (a.slice_state && a.slice_iters > 0) ? a.slice_iters : ss.max_iter;
@@ -819,13 +780,8 @@ inline bool plan_reg(pmpc_context* ctx, const SqpArgs<Model>& a, SqpPlan<Model>&
         // the round-robin kernel and an iteration trace take the build that carries them
         bool modes = a.slice_iters > 0 || ss->iteration_trace != nullptr;
         if constexpr (ONE_ROW && !LEAN) {   // more instances than resident wavefronts: one SQP iteration per work item (PMPC_SQP_RR=1, sqp_kernel_rr)
-#ifdef PMPC_RR_PROFILE
-            const bool rr_phase_ok = true;
-#else
-            const bool rr_phase_ok = !a.phase;
-#endif
-            const int slots = PMPC_SQP_WAVES * pmpc_internal_simd_count(ctx);
-            if (!pol && a.slice_state && a.slice_iters == 0 && rr_phase_ok && ss->max_iter > 1 && ss->max_iter <= RR_MAX_ITER && a.B > slots && a.B <= RR_MAX_BATCH &&
+            const int slots = SQP_WAVES * pmpc_internal_simd_count(ctx);
+            if (!pol && a.slice_state && a.slice_iters == 0 && !a.phase && ss->max_iter > 1 && ss->max_iter <= RR_MAX_ITER && a.B > slots && a.B <= RR_MAX_BATCH &&
                 (size_t)a.B * ss->max_iter < ((size_t)1 << 30) && pmpc_internal_sqp_rr(ctx)) {
                 p.rr = (ss->hessian_update == 1) ? sqp_kernel_rr<Model, NN_, MM_, SQP_BLOCK_BFGS> : sqp_kernel_rr<Model, NN_, MM_, 0>;
                 p.rr_init = sqp_rr_init_kernel<Model>;
@@ -848,14 +804,6 @@ inline bool plan_reg(pmpc_context* ctx, const SqpArgs<Model>& a, SqpPlan<Model>&
             p.route = PMPC_ROUTE_CONDREG; p.kern = kern; p.lds = lds; p.timed = timed;
             if (!pmpc_internal_switch(ctx, PMPC_SW_NO_REDO_LAUNCH)) { p.redo = full; p.redo_lds = lds_full; }
         };
-#if PMPC_EXPERIMENT_COND_SMALL   /* developer experiment (round 6, EXPERIMENTS.md): the CONDENSED register QP on a grid of at most 64 KKT rows — config A on 35 instead of 56 rows; the redo stays on the LDS-resident kernel */
-        if constexpr (ONE_ROW && !LEAN && NNODES == 7 && Model::NP == 0 && Model::NG == 0) {
-            if (!pol && condreg && ss->hessian_update == 0 && !a.phase) {
-                p.route = PMPC_ROUTE_CONDREG; p.kern = sqp_kernel_for<Model, NN_, MM_, SQP_COND>(a.slice_iters > 0 || ss->iteration_trace != nullptr); p.rr = nullptr;
-                p.lds = sqp_kernel_lds_bytes<Model>(a.P, a.S, SqpLdsLayout::Cond1);
-            }
-        }
-#endif
         if constexpr (COND_REG_OK<Model, NN_, MM_>::value) {   // 65..112 variables, at most 64 constraint rows, the default policies
             if (!pol && condreg) {
                 size_t lds;

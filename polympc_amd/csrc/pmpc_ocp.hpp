@@ -33,14 +33,10 @@ struct ChebData {
 
 // STATIC LAYOUT of the register-resident kernels (NN > 0). Their instantiation fixes the node count K = MM / (NX + NG), and with it every size OcpDims derives
 // and every LDS offset of the carve — which the kernels used to compute from cd->P, cd->S at run time all the same (150 scalar multiplies at the kernel head, ~45
-// LDS pointers, most of the 252 scalar values the headline kernel kept in spill lanes: a readlane, its wait state and an add in front of most LDS accesses). Developer switch for the
-// A/B of its stages (profiles/r10_ab_static_layout.txt): 0 run-time sizes and pointers; 1 the sizes are constants of the kernel body (OcpDimsCT); 2 also the
-// addresses: D (with its extra row) and w — the only arrays whose size depends on P, not on the node count — move behind everything node-sized (OcpLds::carve_dw),
+// LDS pointers, most of the 252 scalar values the headline kernel kept in spill lanes: a readlane, its wait state and an add in front of most LDS accesses). Now the
+// sizes are constants of the kernel body (OcpDimsCT), and so are the addresses: D (with its extra row) and w — the only arrays whose size depends on P, not on the node count — move behind everything node-sized (OcpLds::carve_dw),
 // so that every other LDS array sits at a constant offset from byte 0 of LDS (lds_origin, pmpc_qp.hpp). P and S stay run-time values: 7 nodes are (6,1), (3,2), (2,3) or (1,6). What makes the
 // constants valid is the launcher's run-time check `a.P * a.S + 1 == NNODES` (plan_reg, pmpc_launch.hpp). The arithmetic is untouched: bit-identical results.
-#ifndef PMPC_STATIC_LAYOUT
-#define PMPC_STATIC_LAYOUT 2
-#endif
 
 template <class Model>
 struct OcpDims {
@@ -56,7 +52,7 @@ struct OcpDims {
     }
 };
 
-// the same sizes for a node count KN known at compile time (register-resident kernels, PMPC_STATIC_LAYOUT >= 1): constants, read through the same names
+// the same sizes for a node count KN known at compile time (register-resident kernels): constants, read through the same names
 template <class Model, int KN>
 struct OcpDimsCT {
     static_assert(KN > 0, "OcpDimsCT: a compile-time node count");
@@ -70,7 +66,7 @@ struct OcpDimsCT {
 template <class Model, int KN> struct OcpDimsSel { using type = OcpDimsCT<Model, KN>; };
 template <class Model> struct OcpDimsSel<Model, 0> { using type = OcpDims<Model>; };
 // node count an Ocp / OcpLds of a kernel with NN variables and MM constraint rows is built for (0: run-time sizes)
-template <class Model, int NN, int MM> constexpr int static_nodes() { return (PMPC_STATIC_LAYOUT >= 1 && NN > 0) ? MM / (Model::NX + Model::NG) : 0; }
+template <class Model, int NN, int MM> constexpr int static_nodes() { return NN > 0 ? MM / (Model::NX + Model::NG) : 0; }
 // a loop bound the compiler must treat as a run-time value: the cold loops of the kernel heads and tails (prologue loads, stage_constants, epilogue stores) stay
 // rolled — unrolled by a known trip count they issue their loads in bulk and cost the headline kernel its last ten registers (256 + scratch)
 template <bool OPAQUE> __device__ __forceinline__ int rolled_bound(int v) {
@@ -82,7 +78,7 @@ template <bool OPAQUE> __device__ __forceinline__ int rolled_bound(int v) {
 template <class Model, int KN = 0>
 struct OcpLds {
     using Dm = typename OcpDimsSel<Model, KN>::type;
-    static constexpr bool TAIL_DW = KN > 0 && PMPC_STATIC_LAYOUT >= 2;   // D / w carved by carve_dw, behind everything node-sized
+    static constexpr bool TAIL_DW = KN > 0;   // D / w carved by carve_dw, behind everything node-sized
     enum { NX = Dm::NX, NU = Dm::NU, NP = Dm::NP, NG = Dm::NG, NDER = Dm::NDER };
     double *D, *w, *tn;                                 // collocation constants; D is followed by Dl[t] = -D(0, P - t), the last node's row of J (:845-846)
     double *nd, *nw1, *nw2; int* nsr;                   // per node: D self entry, the two quadrature weights * t_scale, packed (flags, segment, row)

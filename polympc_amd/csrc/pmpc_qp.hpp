@@ -17,10 +17,7 @@
 namespace pmpc {
 
 constexpr int WAVE = 64;
-#ifndef PMPC_BIG_MEM_BATCH
-#define PMPC_BIG_MEM_BATCH 32
-#endif
-constexpr int BIG_MEM_BATCH = PMPC_BIG_MEM_BATCH;   // loads in flight per lane in the row walks of the HBM-factor kernels (BFGS products and update, H x of the residuals): one memory round trip per batch
+constexpr int BIG_MEM_BATCH = 32;   // loads in flight per lane in the row walks of the HBM-factor kernels (BFGS products and update, H x of the residuals): one memory round trip per batch
 constexpr double RHO_MIN = 1e-6, RHO_MAX = 1e+6, RHO_EQ_FACTOR = 1e+3;   // box_admm.hpp:56-59
 constexpr double LOOSE_BOUNDS_THRESH = 1e+10, EQ_TOL = 1e-4;            // qp_base.hpp:124-125
 constexpr double DIV_BY_ZERO_REGUL = 10e-10;                            // qp_base.hpp:79-82
@@ -37,7 +34,7 @@ __device__ __forceinline__ int lane_id() { int l = threadIdx.x & (WAVE - 1); asm
 __device__ __forceinline__ void wfence() { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); }
 __device__ __forceinline__ void wsync() { wfence(); __builtin_amdgcn_wave_barrier(); }
 
-// Origin of a kernel's dynamic LDS for a carve at constant offsets (PMPC_STATIC_LAYOUT >= 2, pmpc_ocp.hpp). The address of an `extern __shared__` array reaches
+// Origin of a kernel's dynamic LDS for a carve at constant offsets (static layout, pmpc_ocp.hpp). The address of an `extern __shared__` array reaches
 // instruction selection as an opaque "static LDS size" node: every `smem + constant` becomes a scalar add of its own, hoisted to the kernel head and kept in — or
 // spilled from — an SGPR (118 of them in the headline kernel), and no constant reaches the offset field of a ds instruction. LITERAL = true: the origin as the
 // integer it is — byte 0 of LDS, these kernels declare no static __shared__ variable (tests/test_static_layout_cpu.py reads .group_segment_fixed_size = 0 of every

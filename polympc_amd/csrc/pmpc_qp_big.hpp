@@ -540,10 +540,7 @@ __device__ __forceinline__ void big_solve(const double* W, int N, double* v, dou
     const size_t nt = (size_t)BigKkt::ntiles(N);
     const double* LF = W + nt * 256;
     if constexpr (NW > 1) { big_solve_team<NW>(LF, N, nb, NPAD, v, bx, team); return; }
-#ifndef PMPC_BIG_GS
-#define PMPC_BIG_GS 4
-#endif
-    constexpr int GS = SLIM ? 2 : PMPC_BIG_GS;   // row slots (of 64 rows) whose loads are issued together
+    constexpr int GS = SLIM ? 2 : 4;   // row slots (of 64 rows) whose loads are issued together
     // ---- forward: blocks ascending; inside a block columns ascending. No entry of L depends on the solution, only the fma chains do: the panel of a block
     // column is requested BEFORE the triangular solve with its diagonal tile, and the diagonal tile of the next block column with it (two register sets,
     // alternating: the block loop is unrolled by two so that neither set is ever copied) — a block step exposed two memory round trips, now the first
@@ -633,10 +630,7 @@ __device__ __forceinline__ void big_solve(const double* W, int N, double* v, dou
     // the rows below the block are column dot products — every lane keeps one partial sum per column over its rows (row 16(J+1) + 64 g + lane,
     // g ascending, fma); the 64 partials of a column are added in four groups of 16 (lane (c, k) adds group k of column c in index order), the
     // group sums as (S0 + S1) + (S2 + S3) — subtracted once; then the block's own triangle, columns descending. (CPU restatement: PIVOT_BLOCKED.)
-#ifndef PMPC_BIG_GB
-#define PMPC_BIG_GB 4
-#endif
-    constexpr int GB = SLIM ? 2 : PMPC_BIG_GB;     // row slots in flight (16 running sums per lane on top of the loaded entries; 4: one batch per block column up to 272 rows)
+    constexpr int GB = SLIM ? 2 : 4;     // row slots in flight (16 running sums per lane on top of the loaded entries; 4: one batch per block column up to 272 rows)
     double* red = bx + 16;    // 16 x 64 partial sums, column stride 65 (conflict-free for the column-parallel group sums)
     double* grp = red + 16 * 65; // 4 x 16 group sums
     size_t oFb = BigKkt::offF(nb, NPAD);

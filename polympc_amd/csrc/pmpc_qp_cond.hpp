@@ -24,14 +24,12 @@
 
 namespace pmpc {
 
-#ifndef PMPC_COND_NV
-#define PMPC_COND_NV 25
-#endif
-// the swept inverse of S: the two-rows-per-lane tile set with PMPC_COND_NV of its operand tiles in arch VGPRs (25 tiles at 66..80 rows: the rest lives
+constexpr int COND_NV = 25;
+// the swept inverse of S: the two-rows-per-lane tile set with COND_NV of its operand tiles in arch VGPRs (25 tiles at 66..80 rows: the rest lives
 // in the accumulation file and costs two v_accvgpr_read per entry and ADMM iteration)
-template <int NN, bool SMALL = (NN <= WAVE)> struct CondKktSel { using type = RegKkt2<NN, PMPC_COND_NV>; };
+template <int NN, bool SMALL = (NN <= WAVE)> struct CondKktSel { using type = RegKkt2<NN, COND_NV>; };
 // at most 64 variables — grids of 65..128 KKT rows whose primal block fits one row per lane: the one-row-per-lane tile set of pmpc_qp_reg.hpp (16 tiles
-// = 128 registers, a register-only DPP mat-vec); one wavefront per SIMD like the large variant (PMPC_COND1_WAVES, pmpc_launch.hpp: measured)
+// = 128 registers, a register-only DPP mat-vec); one wavefront per SIMD like the large variant (COND1_WAVES, pmpc_launch.hpp: measured)
 template <int NN> struct CondKktSel<NN, true> { using type = RegKkt<NN>; };
 template <int NN> using CondKkt = typename CondKktSel<NN>::type;
 
@@ -42,7 +40,7 @@ struct CondDims {
     static constexpr int N = NN + MM;
     static constexpr bool SMALL = NN <= WAVE;
     static constexpr int SL = SMALL ? 1 : 2;                      // primal slots per lane
-    static constexpr int RHS_OFF = []() constexpr { if constexpr (NN <= WAVE) return 0; else return (int)RegKkt2<NN, PMPC_COND_NV>::RHS_OFF; }();
+    static constexpr int RHS_OFF = []() constexpr { if constexpr (NN <= WAVE) return 0; else return (int)RegKkt2<NN, COND_NV>::RHS_OFF; }();
     static constexpr int US_OFF = RHS_OFF + 128;                  // rho o r2 / y (MM entries) behind the rhs exchange buffer of RegKkt2::apply
     static constexpr int XS_OFF = US_OFF + 64;                    // x (NN entries)
     static constexpr int PB_OFF = XS_OFF + 128;                   // residual evaluation: products of the few primal rows of the second slot

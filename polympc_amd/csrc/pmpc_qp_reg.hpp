@@ -18,11 +18,9 @@
 #include <hip/hip_runtime.h>
 #include "pmpc_qp.hpp"
 
-#ifndef PMPC_REG_RESIDUAL_BATCH
-#define PMPC_REG_RESIDUAL_BATCH 14
-#endif
-
 namespace pmpc {
+
+constexpr int REG_RESIDUAL_BATCH = 14;   // loads in flight per lane in a residual evaluation of boxadmm_solve_reg
 
 __device__ __forceinline__ double bcast_lane(double v, int lane) {
     const int lo = __builtin_amdgcn_readlane(__double2loint(v), lane);
@@ -41,13 +39,8 @@ __device__ __forceinline__ void sched_fence() { __builtin_amdgcn_sched_barrier(0
 // emitted with every lane enabled. That is a property of the BUILT code, and it is checked there: tests/tools_exec_regions.py follows EXEC (and every saved
 // copy of it, through SGPR spill lanes too) over the control-flow graph of each shipped kernel and proves that every one of these bodies starts at full EXEC
 // (tests/test_kernel_occupancy_cpu.py). Round 6 examined it as the suspect behind round 5's miscompiled hook build (EXPERIMENTS.md): refuted — in that build
-// too every body starts at full EXEC, and the fault is identical with each of the forms below (it is a VGPR -> AGPR live-range split of the lane id that the
-// compiler placed inside the else-block of a divergent if / else: the same test now checks the built code for that pattern as well).
-// PMPC_PIVOT_SETUP_FORM (developer switch of that experiment): 0 the shipped form; 1 the same as `asm volatile`; 2 EXEC saved in an SGPR pair and restored
-// from it (correct under any EXEC); 3 no EXEC write at all: v_cndmask selects on lane == k.
-#ifndef PMPC_PIVOT_SETUP_FORM
-#define PMPC_PIVOT_SETUP_FORM 0
-#endif
+// too every body starts at full EXEC, and the fault is identical with an EXEC save / restore and with no EXEC write at all (it is a VGPR -> AGPR live-range
+// split of the lane id that the compiler placed inside the else-block of a divergent if / else: the same test now checks the built code for that pattern as well).
 __device__ __forceinline__ void pivot_lane_setup(double& a0, double& a1, double& a2, double& a3, double& a4, double& a5, double& a6, double& l,
                                                  double lk, int k) {
     asm("s_lshl_b64 exec, 1, %9\n\tv_mov_b64 %0, 0\n\tv_mov_b64 %1, 0\n\tv_mov_b64 %2, 0\n\tv_mov_b64 %3, 0\n\tv_mov_b64 %4, 0\n\tv_mov_b64 %5, 0\n\t"
@@ -55,20 +48,8 @@ __device__ __forceinline__ void pivot_lane_setup(double& a0, double& a1, double&
         : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5), "+v"(a6), "+v"(l) : "v"(lk), "i"(k) : "scc");
 }
 __device__ __forceinline__ void pivot_lane_setup(double& a0, double& a1, double& a2, double& l, double lk, int k) {
-#if PMPC_PIVOT_SETUP_FORM == 1
-    asm volatile("s_lshl_b64 exec, 1, %5\n\tv_mov_b64 %0, 0\n\tv_mov_b64 %1, 0\n\tv_mov_b64 %2, 0\n\tv_mov_b64 %3, %4\n\ts_mov_b64 exec, -1"
-        : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(l) : "v"(lk), "i"(k) : "scc");
-#elif PMPC_PIVOT_SETUP_FORM == 2
-    unsigned long long saved, win;
-    asm volatile("s_mov_b64 %4, exec\n\ts_lshl_b64 %5, 1, %7\n\ts_and_b64 exec, %4, %5\n\tv_mov_b64 %0, 0\n\tv_mov_b64 %1, 0\n\tv_mov_b64 %2, 0\n\tv_mov_b64 %3, %6\n\ts_mov_b64 exec, %4"
-        : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(l), "=&s"(saved), "=&s"(win) : "v"(lk), "i"(k) : "scc");
-#elif PMPC_PIVOT_SETUP_FORM == 3
-    const bool me = lane_id() == k;
-    a0 = me ? 0.0 : a0; a1 = me ? 0.0 : a1; a2 = me ? 0.0 : a2; l = me ? lk : l;
-#else
     asm("s_lshl_b64 exec, 1, %5\n\tv_mov_b64 %0, 0\n\tv_mov_b64 %1, 0\n\tv_mov_b64 %2, 0\n\tv_mov_b64 %3, %4\n\ts_mov_b64 exec, -1"
         : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(l) : "v"(lk), "i"(k) : "scc");
-#endif
 }
 // 1 / d, branch-free: the generic IEEE division expansion (v_rcp_f64, two Newton steps, residual correction, v_div_fixup for
 // 0 / inf / NaN) WITHOUT its v_div_scale pre-scaling — 8 VALU operations instead of 12. The pre-scaling only matters when d or
@@ -100,13 +81,8 @@ __device__ __forceinline__ unsigned lane_id_near(int zo) {
     return l;
 }
 
-// RESIDUAL TRIM (boxadmm_solve_reg, residuals_update): fewer issue slots per residual evaluation, not one bit of any residual changed. Developer switch for
-// the A/B of its stages (profiles/*_ab_residual_trim.txt): 0 five wave_max and an address computed in front of every load; 1 the five norms in one
-// transposed reduction (wave_max5); 2 on the stacked workspace also the addresses of an evaluation from two per-lane offsets computed once
-// (StackedResidualAddr).
-#ifndef PMPC_RESIDUAL_TRIM
-#define PMPC_RESIDUAL_TRIM 2
-#endif
+// RESIDUAL TRIM (boxadmm_solve_reg, residuals_update): fewer issue slots per residual evaluation, not one bit of any residual changed: the five norms in one
+// transposed reduction (wave_max5) and, on the stacked workspace, the addresses of an evaluation from two per-lane offsets computed once.
 // The byte offsets of one evaluation's loads into the stacked (NN + MM) x NN column-major workspace [H; A] (uniform base ws): row `lane` is read at NN
 // columns 8 N bytes apart, column `lane` of A at MM consecutive doubles. Every load is  global_load  ws (scalar pair) + offset (one VGPR) + immediate; the
 // immediate is 13 bits signed, so a row base sits in the middle of every W = 2 SPAN + 1 columns and reaches SPAN columns to either side (35 + 21: two bases
@@ -135,13 +111,11 @@ struct StackedResidualAddr {
 };
 
 // DIRECT TILE STAGING (RegKkt::invert, constraint-first mode): the KKT tiles and the operands of the rank-m update are loaded from the stacked
-// [H; A] workspace straight in MFMA layout, instead of row-per-lane and transposed through LDS. Developer switch for the A/B of its stages
-// (profiles/*_ab_direct_tile_staging.txt): 0 the row path; 1 the all-primal tile components; 2 every tile component; 3 the rank-m operands too.
-#ifndef PMPC_DIRECT_STAGING
-#define PMPC_DIRECT_STAGING 3
-#endif
+// [H; A] workspace straight in MFMA layout, instead of row-per-lane and transposed through LDS.
 // The tile source of that path: ws = the (NPIV + MC) x NPIV column-major array [H; A] (leading dimension N), H BITWISE SYMMETRIC (entry (i, j) of
-// the primal block is read as H(j, i): the sixteen lanes of a tile row then read one 128-byte line). kcol: the row path's loader (stages 0 .. 2).
+// the primal block is read as H(j, i): the sixteen lanes of a tile row then read one 128-byte line). kcol: the row path's loader. UNUSED: the direct
+// path never calls it. Removing the member (or the `rowload` binding in invert) changes no instruction but renumbers the registers of ten small-grid
+// kernels; take both out in the next change that is allowed to alter device code.
 template <class KCol>
 struct StackedTileSource { const double* ws; KCol kcol; };
 template <class T> struct is_stacked_tile_source { static constexpr bool value = false; };
@@ -283,34 +257,28 @@ struct RegKkt {
         // of X, beyond the exchange rows) and is written BEFORE the loads are issued: held in a register it was spilled,
         // and a scratch reload waits on vmcnt behind every outstanding load.
         X[64 * SX + ln] = diag;
-        // DIRECT (a StackedTileSource in place of kcol, see PMPC_DIRECT_STAGING): component r of tile (R, C) is entry (i, j) = (16R + 4r + lr, 16C + lc) of
+        // DIRECT (a StackedTileSource in place of kcol): component r of tile (R, C) is entry (i, j) = (16R + 4r + lr, 16C + lc) of
         //   primal row i:      ws[i*N + j]  = H(j, i) (= H(i, j) bitwise) for j < NPIV, A(j - NPIV, i) beyond — scaled by -rho_j there (diagonal tiles only);
         //   constraint row i:  ws[j*N + i]  = A(i - NPIV, j), scaled by -rho_i;  columns j >= NPIV: exact zeros;  padding rows i >= N: row 0, as the row path's clamp;
         // a per-lane base (lr*N + lc or lc*N + lr) plus a compile-time constant. rho by row / by column comes from the LDS vector RH (one write, broadcast reads).
-        // Everything lane-dependent is a select (address or value), never a branch. The operands of the rank-m update (stage 3) are loaded in the same batch.
+        // Everything lane-dependent is a select (address or value), never a branch. The operands of the rank-m update are loaded in the same batch.
         constexpr bool DIRECT = is_stacked_tile_source<KCol>::value;
-        constexpr int DS = DIRECT ? PMPC_DIRECT_STAGING : 0;
         static_assert(!DIRECT || (CF && !EST && BK * SK + XSZ + 64 <= TRI), "direct tile staging: constraint-first mode without the conditioning gate");
-        constexpr int MCD = N - NPIV, KSD = (MCD + 3) / 4, NTPD = (NPIV + 15) / 16;
+        constexpr int MC = N - NPIV, KS = (MC + 3) / 4, NTP = (NPIV + 15) / 16;   // constraint rows, their groups of four, primal tile rows
         double* RH = st + BK * SK + XSZ;   // rho of every lane (free until the final conversion)
-        if constexpr (DS >= 2) RH[ln] = rho_self;
+        if constexpr (DIRECT) RH[ln] = rho_self;
         auto rowsP = [](int R, int r) constexpr { return 16 * R + 4 * r + 3 < NPIV; };    // the four rows of component r of tile row R: all primal
         auto rowsC = [](int R, int r) constexpr { return 16 * R + 4 * r >= NPIV; };       // ... none primal
         auto colsP = [](int C) constexpr { return 16 * C + 15 < NPIV; };                  // the sixteen columns of tile column C: all primal
-        auto direct = [&](int R, int C, int r) constexpr { return DS >= 2 || (DS == 1 && rowsP(R, r) && colsP(C)); };
         sched_fence();
         int z = 0;
         asm volatile("" : "+v"(z));
-        auto&& rowload = [&]() -> auto& { if constexpr (DIRECT) return kcol.kcol; else return kcol; }();
-        if constexpr (DS < 2) {
+        auto&& rowload = [&]() -> auto& { if constexpr (DIRECT) return kcol.kcol; else return kcol; }();   // the row path's loader (bound on the direct path too: see StackedTileSource)
+        [[maybe_unused]] double ov[DIRECT ? KS * NTP : 1];
+        if constexpr (!DIRECT) {
 #pragma unroll
             for (int j = 0; j < NP; ++j) a[j] = (j < N) ? rowload(j < N ? j : 0, z) : 0.0;
-        } else if constexpr (DS == 2) {   // the raw A columns of the rank-m update
-#pragma unroll
-            for (int j = NPIV; j < N; ++j) a[j] = rowload(j, z);
-        }
-        [[maybe_unused]] double ov[DS == 3 ? KSD * NTPD : 1];
-        if constexpr (DS >= 1) {
+        } else {
             const unsigned l = lane_id_near(z), dlr = l >> 4, dlc = l & 15;
             unsigned bP = dlr * N + dlc + (unsigned)z, bC = dlc * N + dlr + (unsigned)z;
             asm("" : "+v"(bP));
@@ -321,7 +289,6 @@ struct RegKkt {
                 for (int C = 0; C <= R; ++C)
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
-                        if (!direct(R, C, r)) continue;
                         const int i0 = 16 * R + 4 * r, j0 = 16 * C;
                         // primal rows: column j < N always holds below the diagonal tile of a primal tile row; clamp in the diagonal tile if it reaches past N
                         const unsigned oP = (j0 + 15 < N) ? bP + (unsigned)(i0 * N + j0) : (j0 + dlc < (unsigned)N ? bP + (unsigned)(i0 * N + j0) : 0u);
@@ -331,44 +298,43 @@ struct RegKkt {
                         const unsigned o = rowsP(R, r) ? oP : (rowsC(R, r) ? oC : (i0 + dlr < (unsigned)NPIV ? oP : oC));
                         T[R][C][r] = kcol.ws[o];
                     }
-            if constexpr (DS == 3) {   // A(4s + lr, 16R + lc) at (16R + lc)*N + NPIV + 4s + lr: the operand layout of the rank-m update
+            // A(4s + lr, 16R + lc) at (16R + lc)*N + NPIV + 4s + lr: the operand layout of the rank-m update
 #pragma unroll
-                for (int s2 = 0; s2 < KSD; ++s2)
+            for (int s2 = 0; s2 < KS; ++s2)
 #pragma unroll
-                    for (int R = 0; R < NTPD; ++R) {
-                        const bool in = (4 * s2 + 3 < MCD || 4 * s2 + dlr < (unsigned)MCD) && (16 * R + 15 < NPIV || 16 * R + dlc < (unsigned)NPIV);
-                        const unsigned o = in ? bC + (unsigned)(16 * R * N + NPIV + 4 * s2) : 0u;
-                        ov[s2 * NTPD + R] = kcol.ws[o];
-                    }
-            }
+                for (int R = 0; R < NTP; ++R) {
+                    const bool in = (4 * s2 + 3 < MC || 4 * s2 + dlr < (unsigned)MC) && (16 * R + 15 < NPIV || 16 * R + dlc < (unsigned)NPIV);
+                    const unsigned o = in ? bC + (unsigned)(16 * R * N + NPIV + 4 * s2) : 0u;
+                    ov[s2 * NTP + R] = kcol.ws[o];
+                }
         }
         sched_fence();
         const bool isPl = ln < NPIV;
-        if constexpr (CF && DS < 2) {   // constraint lanes: row NPIV + j of the swept matrix is -rho_j A_j
+        if constexpr (!DIRECT) {
+            if constexpr (CF) {   // constraint lanes: row NPIV + j of the swept matrix is -rho_j A_j
 #pragma unroll
-            for (int j = 0; j < NPIV; ++j) { const double sc = -(rho_self * a[j]); a[j] = isPl ? a[j] : sc; }
-        }
-        if constexpr (DS < 2) {
+                for (int j = 0; j < NPIV; ++j) { const double sc = -(rho_self * a[j]); a[j] = isPl ? a[j] : sc; }
+            }
 #pragma unroll
-        for (int g = 0; g < NP / SG; ++g) {
+            for (int g = 0; g < NP / SG; ++g) {
 #pragma unroll
-            for (int t = 0; t < SG; ++t) {
-                double v = a[g * SG + t];
-                if constexpr (CF) {   // primal lanes, constraint columns that share a tile with primal rows (the only ones ever read from a primal lane): -rho_j A(j, lane); a[] keeps the raw entry
-                    if (g * SG + t >= NPIV && g * SG + t < N && 16 * ((g * SG + t) / 16) < NPIV) { const double sc = -(bcast_lane(rho_self, (g * SG + t < N) ? g * SG + t : 0) * v); v = isPl ? sc : v; }
+                for (int t = 0; t < SG; ++t) {
+                    double v = a[g * SG + t];
+                    if constexpr (CF) {   // primal lanes, constraint columns that share a tile with primal rows (the only ones ever read from a primal lane): -rho_j A(j, lane); a[] keeps the raw entry
+                        if (g * SG + t >= NPIV && g * SG + t < N && 16 * ((g * SG + t) / 16) < NPIV) { const double sc = -(bcast_lane(rho_self, (g * SG + t < N) ? g * SG + t : 0) * v); v = isPl ? sc : v; }
+                    }
+                    X[ln * SX + t] = v;
                 }
-                X[ln * SX + t] = v;
-            }
-            lds_order();
-            if ((lc >> 3) == (g % 2)) {
+                lds_order();
+                if ((lc >> 3) == (g % 2)) {
 #pragma unroll
-                for (int R = g / 2; R < NT; ++R)
+                    for (int R = g / 2; R < NT; ++R)
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) if (!direct(R, g / 2, r)) T[R][g / 2][r] = X[(16 * R + lr + 4 * r) * SX + (lc & 7)];
+                        for (int r = 0; r < 4; ++r) T[R][g / 2][r] = X[(16 * R + lr + 4 * r) * SX + (lc & 7)];
+                }
+                lds_order();
+                sched_fence();
             }
-            lds_order();
-            sched_fence();
-        }
         } else {   // scale the directly loaded components
             lds_order();
 #pragma unroll
@@ -402,8 +368,7 @@ struct RegKkt {
         }
         lds_order();
         if constexpr (CF) {   // rank-(N - NPIV) update of the primal tiles: T(a, b) <- fma(rho_j A(j, a), A(j, b), T(a, b)), j ascending (one k-step of the matrix cores per 4 constraints)
-            constexpr int MC = N - NPIV, KS = (MC + 3) / 4, NTP = (NPIV + 15) / 16;
-            if constexpr (DS == 3) {   // operands straight from the batch above: bv = A(4s + lr, 16R + lc) on primal columns, av = rho_j * bv, zeros elsewhere
+            if constexpr (DIRECT) {   // operands straight from the batch above: bv = A(4s + lr, 16R + lc) on primal columns, av = rho_j * bv, zeros elsewhere
 #pragma unroll
                 for (int s2 = 0; s2 < KS; ++s2) {
                     const bool jin = 4 * s2 + 3 < MC || 4 * s2 + lr < MC;
@@ -423,27 +388,27 @@ struct RegKkt {
                 }
             } else {
 #pragma unroll
-            for (int s2 = 0; s2 < KS; ++s2) {
+                for (int s2 = 0; s2 < KS; ++s2) {
 #pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                    const int j = 4 * s2 + t;
-                    const double raw = (j < MC) ? a[(NPIV + j < NP) ? NPIV + j : 0] : 0.0;
-                    const double rj = (j < MC) ? bcast_lane(rho_self, (NPIV + j < N) ? NPIV + j : 0) : 0.0;
-                    const double pa = rj * raw;
-                    PA[t * SK + ln] = (isPl && j < MC) ? pa : 0.0;
-                    PB[t * SK + ln] = (isPl && j < MC) ? raw : 0.0;
+                    for (int t = 0; t < 4; ++t) {
+                        const int j = 4 * s2 + t;
+                        const double raw = (j < MC) ? a[(NPIV + j < NP) ? NPIV + j : 0] : 0.0;
+                        const double rj = (j < MC) ? bcast_lane(rho_self, (NPIV + j < N) ? NPIV + j : 0) : 0.0;
+                        const double pa = rj * raw;
+                        PA[t * SK + ln] = (isPl && j < MC) ? pa : 0.0;
+                        PB[t * SK + ln] = (isPl && j < MC) ? raw : 0.0;
+                    }
+                    lds_order();
+                    double av[NTP], bv[NTP];
+#pragma unroll
+                    for (int R = 0; R < NTP; ++R) { av[R] = PA[lr * SK + 16 * R + lc]; bv[R] = PB[lr * SK + 16 * R + lc]; }
+#pragma unroll
+                    for (int R = 0; R < NTP; ++R)
+#pragma unroll
+                        for (int C = 0; C <= R; ++C) T[R][C] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[R], bv[C], T[R][C], 0, 0, 0);
+                    sched_fence();
+                    lds_order();
                 }
-                lds_order();
-                double av[NTP], bv[NTP];
-#pragma unroll
-                for (int R = 0; R < NTP; ++R) { av[R] = PA[lr * SK + 16 * R + lc]; bv[R] = PB[lr * SK + 16 * R + lc]; }
-#pragma unroll
-                for (int R = 0; R < NTP; ++R)
-#pragma unroll
-                    for (int C = 0; C <= R; ++C) T[R][C] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[R], bv[C], T[R][C], 0, 0, 0);
-                sched_fence();
-                lds_order();
-            }
             }
         }
         pre(T, PA, PB, ln, lr, lc);
@@ -677,11 +642,10 @@ __device__ __forceinline__ void boxadmm_solve_reg(const double* __restrict__ H, 
         else return colA[k + zo];
     };
     constexpr int LDH = STACKED ? N : NN;
-    // PMPC_RESIDUAL_TRIM >= 2, stacked workspace: the residual evaluations (and the z = A x_guess product) take their addresses from the two per-lane offsets of
+    // Stacked workspace: the residual evaluations (and the z = A x_guess product) take their addresses from the two per-lane offsets of
     // StackedResidualAddr, built once per evaluation. The per-lane base and stride of the QP entry kernels already share ONE stride + opaque-zero term among
     // the loads of an evaluation (their columns are a 64-bit multiply-add away, there is no immediate to reach them by), and the staging loaders of invert()
     // (kcol: Krow, KrowLower, Acol, called load by load from inside RegKkt::invert) keep the per-load form.
-    constexpr bool TRIM_ADDR = STACKED && PMPC_RESIDUAL_TRIM >= 2;
 
     // state: xv = x (primal lanes) / z (constraint lanes); yv = y_box / y_a; qv = q (primal lanes)
     double xv = 0.0, yv = 0.0, qv = 0.0;
@@ -691,7 +655,7 @@ __device__ __forceinline__ void boxadmm_solve_reg(const double* __restrict__ H, 
     }
     if (x0) {  // z = A * x_guess
         double acc = 0.0;
-        if constexpr (TRIM_ADDR) {
+        if constexpr (STACKED) {
             const StackedResidualAddr<NN, MM> ad(lane_id_near(0), 0);
 #pragma unroll
             for (int j = 0; j < NN; ++j) acc += ad.krow(H, j) * bcast_lane(xv, j);
@@ -745,7 +709,7 @@ __device__ __forceinline__ void boxadmm_solve_reg(const double* __restrict__ H, 
             // Direct tile staging where its preconditions hold: the stacked workspace of the fused SQP kernels with an H they wrote bitwise symmetric (dense
             // BFGS, exact Hessian) and no conditioning gate. SYMLOWER (block BFGS, Ruiz-scaled H) and the caller's H of the QP entry kernels keep the row path.
             bool tripped;
-            if constexpr (STACKED && !SYMLOWER && !GATE && PMPC_DIRECT_STAGING != 0) tripped = K.template invert<NN, GATE>(ln, tr, kdiag, StackedTileSource<decltype(kcol)>{H, kcol}, tm, rhov);
+            if constexpr (STACKED && !SYMLOWER && !GATE) tripped = K.template invert<NN, GATE>(ln, tr, kdiag, StackedTileSource<decltype(kcol)>{H, kcol}, tm, rhov);
             else tripped = K.template invert<NN, GATE>(ln, tr, kdiag, kcol, tm, rhov);
             if constexpr (GATE) { if (tripped) { status = GAVE_UP; running = false; if (dbg) dbg[0] += clock64() - f0; break; } }
             if (dbg) dbg[0] += clock64() - f0;
@@ -782,20 +746,20 @@ __device__ __forceinline__ void boxadmm_solve_reg(const double* __restrict__ H, 
                 // loads in chunks of RC columns (independent, coalesced), each followed by its slice of the mat-vec chain
                 // H / A row and A column in ONE list of NN + MM entries, RC at a time: the loads are L2 round trips (~2 k cycles each batch) and
                 // the two mat-vec chains keep their ascending order whatever the batching
-                constexpr int RC = PMPC_REG_RESIDUAL_BATCH;
+                constexpr int RC = REG_RESIDUAL_BATCH;
                 int zr = 0;            // opaque zero added to the addresses: keeps these loop-invariant loads inside the loop
                 asm volatile("" : "+v"(zr));
                 double acc = 0.0;      // lanes < n: (H x)_i ; lanes in [n, N): (A x)_r
                 double aty = 0.0;      // lanes < n: (A^T y_a)_i
-                const unsigned lnear = PMPC_RESIDUAL_TRIM >= 1 ? lane_id_near(zr) : 0u;   // one re-materialised lane id per evaluation (addresses, the packed reduction)
-                const StackedResidualAddr<NN, MM> ad(lnear, zr);                         // (dead unless TRIM_ADDR)
+                const unsigned lnear = lane_id_near(zr);   // one re-materialised lane id per evaluation (addresses, the packed reduction)
+                const StackedResidualAddr<NN, MM> ad(lnear, zr);                         // (dead unless STACKED)
 #pragma unroll
                 for (int e0 = 0; e0 < N; e0 += RC) {
                     double mv[RC];
 #pragma unroll
                     for (int e = 0; e < RC; ++e) {
                         const int ee = e0 + e;
-                        if constexpr (TRIM_ADDR) mv[e] = (ee < NN) ? ad.krow(H, ee < NN ? ee : 0) : ((ee < N) ? ad.acol(H, (ee >= NN && ee < N) ? ee - NN : 0) : 0.0);
+                        if constexpr (STACKED) mv[e] = (ee < NN) ? ad.krow(H, ee < NN ? ee : 0) : ((ee < N) ? ad.acol(H, (ee >= NN && ee < N) ? ee - NN : 0) : 0.0);
                         else mv[e] = (ee < NN) ? Krow(ee < NN ? ee : 0, zr) : ((ee < N) ? Acol((ee >= NN && ee < N) ? ee - NN : 0, zr) : 0.0);
                     }
 #pragma unroll
@@ -815,8 +779,7 @@ __device__ __forceinline__ void boxadmm_solve_reg(const double* __restrict__ H, 
                 double rp = isC ? fabs(acc - xv) : 0.0, rq = isP ? fabs(xv - qv) : 0.0;
                 double rd = isP ? fabs(((acc + hv) + aty) + yv) : 0.0;
                 // five maxima of absolute values: one transposed reduction (9 exchange steps) instead of five six-step ones
-                if constexpr (PMPC_RESIDUAL_TRIM >= 1) wave_max5(nA, nH, rp, rq, rd, lnear);
-                else { nA = wave_max(nA); nH = wave_max(nH); rp = wave_max(rp); rq = wave_max(rq); rd = wave_max(rd); }
+                wave_max5(nA, nH, rp, rq, rd, lnear);
                 max_Ax_z_norm = nA;
                 max_Hx_ATy_h_norm = nH;
                 res_prim = rp + rq;

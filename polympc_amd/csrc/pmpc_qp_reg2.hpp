@@ -52,11 +52,9 @@ struct RegKkt2 {
     static constexpr int LT = NL * 256;                       // doubles of LDS tiles; the small buffer YS sits behind them
     static constexpr int YS = 16 * SY;
     static constexpr int TRI1 = TRI0 > NT * 16 * SY ? TRI0 : NT * 16 * SY;
-#ifndef PMPC_REG2_LDSPARK
-#define PMPC_REG2_LDSPARK 9   /* operand tiles parked in LDS while the residuals are evaluated (config B: 0 / 6 / 9 -> 38.4 / 37.0 / ... ms), see park() */
-#endif
+    static constexpr int LDSPARK = 9;   // operand tiles parked in LDS while the residuals are evaluated (config B: 0 / 6 / 9 -> 38.4 / 37.0 / ... ms), see park()
     // 7 x 7 tiles: room for three more parked tiles behind the staging (6 KB: the largest of these kernels then needs 39.3 KB, four instances per CU still fit)
-    static constexpr int PARK_EXTRA = (NT == 7 && PMPC_REG2_LDSPARK > 6) ? (PMPC_REG2_LDSPARK - 6) * 256 : 0;
+    static constexpr int PARK_EXTRA = (NT == 7 && LDSPARK > 6) ? (LDSPARK - 6) * 256 : 0;
     static constexpr int TRI = LDS_TILES ? (TRI0 > LT + YS ? TRI0 : LT + YS) : TRI1 + PARK_EXTRA;   // doubles of LDS staging (PA | PB aliased with X; Y and the rhs buffer alias both)
     static constexpr int RHS_OFF = LDS_TILES ? LT : 0;        // where apply() stages the right-hand side / the residual evaluation its vectors
     __device__ __forceinline__ static constexpr bool in_lds(int R, int C) { return LDS_TILES && ((R + C) & 3) == 3; }
@@ -354,7 +352,7 @@ struct RegKkt2 {
     __device__ __forceinline__ static constexpr int lds_parked(int used) {
         if (LDS_TILES) return 0;
         const int fit = (TRI - used) / 256;
-        return fit < 0 ? 0 : (fit < PMPC_REG2_LDSPARK ? fit : (PMPC_REG2_LDSPARK < NV ? PMPC_REG2_LDSPARK : NV));
+        return fit < 0 ? 0 : (fit < LDSPARK ? fit : (LDSPARK < NV ? LDSPARK : NV));
     }
     static constexpr int NPARK = NV * 4;
     template <int NLP, int PARK_OFF>
@@ -621,10 +619,7 @@ __device__ __forceinline__ void boxadmm_solve_reg2(const double* __restrict__ H,
             if (s.adaptive_rho) { until_adapt -= nrun; if (until_adapt == 0) { adapt = true; until_adapt = s.adaptive_rho_interval; } }
             if (check || adapt) {  // residuals_update, box_admm.hpp:398-415: one add chain per row, columns ascending
                 const long long r0 = dbg ? clock64() : 0;
-#ifndef PMPC_REG2_RC
-#define PMPC_REG2_RC 22   /* measured on config B: 11 / 17 / 22 / 24 / 33 / 44 loads per batch -> 47.9 / 45.4 / 41.0 / 43.5 / 42.9 / 51.0 ms */
-#endif
-                constexpr int RC = PMPC_REG2_RC;
+                constexpr int RC = 22;   // measured on config B: 11 / 17 / 22 / 24 / 33 / 44 loads per batch -> 47.9 / 45.4 / 41.0 / 43.5 / 42.9 / 51.0 ms
                 int zr = 0;
                 asm volatile("" : "+v"(zr));
                 double acc[2] = {0.0, 0.0}, aty[2] = {0.0, 0.0};
@@ -674,10 +669,7 @@ __device__ __forceinline__ void boxadmm_solve_reg2(const double* __restrict__ H,
                         h1[t] = H[b1];
                     }
                     // rows of the first slot: RCS loads in flight per batch (primal rows only; a constraint row of this slot re-reads row 0)
-#ifndef PMPC_REG2_RCS
-#define PMPC_REG2_RCS 22
-#endif
-                    constexpr int RCS = PMPC_REG2_RCS;
+                    constexpr int RCS = 22;
                     double hx = 0.0;
 #pragma unroll
                     for (int j0 = 0; j0 < NN; j0 += RCS) {

@@ -21,17 +21,9 @@
 #include "pmpc_ruiz.hpp"
 #include "pmpc_admm.hpp"
 
-#ifndef PMPC_EXPERIMENT_FORCE_SYMLOWER
-#define PMPC_EXPERIMENT_FORCE_SYMLOWER 0   /* 1: developer experiment (round 6, EXPERIMENTS.md) — the headline kernel's KKT build reads the LOWER triangle of H only (one address select per load): what any
-                                              half / packed storage of the BFGS matrix would cost on the read side */
-#endif
-// WIDE TERMS (the phases of the fused loop in which few lanes worked): the same operations on the same operands, formed where the lanes are. Developer switch for
-// the A/B of its stages (profiles/*_ab_wide_terms.txt): 0 one row of B per lane in the rank-2 update, one lane per candidate for every term of the line search's
-// sums; 1 the rank-2 update of the dense damped BFGS on the lower triangle, dealt over all 64 lanes (TriDeal, bfgs_update_tri); 2 also the box terms of the line
-// search formed in its node phase, from the registers that hold x + alpha p there (step_size_selection, `wide`).
-#ifndef PMPC_WIDE_TERMS
-#define PMPC_WIDE_TERMS 2
-#endif
+// WIDE TERMS (the phases of the fused loop in which few lanes worked): the same operations on the same operands, formed where the lanes are: the rank-2 update of
+// the dense damped BFGS on the lower triangle, dealt over all 64 lanes (TriDeal, bfgs_update_tri), and the box terms of the line search formed in its node phase,
+// from the registers that hold x + alpha p there (step_size_selection, `wide`).
 namespace pmpc {
 
 // The lower triangle of an n x n matrix dealt over the wavefront: entry t = lane + 64 e (slot e = 0 .. SLOTS-1) of the T = n (n + 1) / 2 entries (i, j), i >= j.
@@ -135,7 +127,7 @@ struct SqpDevice {
     static constexpr bool CND = (VARIANT & SQP_COND) != 0;   // condensed register QP (pmpc_qp_cond.hpp): a two-rows-per-lane kernel (REG2) whose QP inverts S = H + sigma I + rho_box + A' diag(rho) A only
     static constexpr int SCH_P = PS / 256, SCH_S = PS % 256;
     static constexpr bool HOOKS = (NN == 0) || POL;
-    static constexpr int OCP_KN = (PS > 0) ? 0 : static_nodes<Model, NN, MM>();   // node count the kernel's Ocp is built for (PMPC_STATIC_LAYOUT; the block-structured kernels pass P, S as constants anyway)
+    static constexpr int OCP_KN = (PS > 0) ? 0 : static_nodes<Model, NN, MM>();   // node count the kernel's Ocp is built for (static layout, pmpc_ocp.hpp; the block-structured kernels pass P, S as constants anyway)
     using OcpT = Ocp<Model, OCP_KN>;
     using Dm = typename OcpT::Dm;
     // Ruiz scaling is compiled into the kernels that carry the hooks (HOOKS: the LDS / HBM-resident kernels and the hook builds, POL, of the register kernels): in the default
@@ -156,7 +148,7 @@ struct SqpDevice {
     QpLds& qw;
     double* lsbuf = nullptr;   // LDS scratch of the side-by-side line search (aliases the MFMA staging, free outside the QP)
     bool ls_side_by_side = false;   // lsbuf holds G >= 2 candidates
-    bool ls_wide = false;           // ... and behind them the two box terms of every variable of every candidate (PMPC_WIDE_TERMS >= 2)
+    bool ls_wide = false;           // ... and behind them the two box terms of every variable of every candidate (wide terms)
     bool cb_valid = false;     // v.cb holds the constraint values of the CURRENT iterate (set by the line search)
     double* tr = nullptr;  // LDS transpose scratch of the register-resident QP (aliases the per-node AD staging, dead during the QP)
     double* Hw;  // H(i,j) = Hw[j*ldw + i]  — upper block of the stacked (n+m) x n HBM workspace [H ; J]
@@ -185,9 +177,6 @@ struct SqpDevice {
     __device__ __forceinline__ static long long now() { if constexpr (PROF) return clock64(); else return 0; }
     __device__ __forceinline__ void acc(int i, long long dt) { if constexpr (PROF) cyc[i] += dt; }   // shader-clock cycles: 0 linearise(+BFGS) 1 QP 2 line search 3 termination 4 total 5 BFGS 6 KKT build+factor 7 QP residuals 8 ls node evaluation 9 ls scalar sums 10 first-order staging 11 second-order staging 12 first-order assembly 13 Hessian assembly 14 Lagrangian gradient 16..20 KKT inverse: row loads+staging, panel moves, sweeps, MFMA updates, final conversion 21 ls prologue (mu, grad'p) 22 ls acceptance
 
-#ifdef PMPC_EXPERIMENT_WG_STAMPS
-    long long t_start_stamp = wall_clock64();
-#endif
     __device__ SqpDevice(OcpT& o, SqpLds& v_, QpLds& q_, double* H_, double* A_, const pmpc_sqp_settings& s, const pmpc_qp_settings& q)
         : ocp(o), v(v_), qw(q_), Hw(H_), Aw(A_), ldw(o.dm.n + o.dm.m), ss(s), qs(q), n(rolled_bound<(OCP_KN > 0)>(o.dm.n)), m(rolled_bound<(OCP_KN > 0)>(o.dm.m)),
           me(rolled_bound<(OCP_KN > 0)>(o.dm.me)), mi(rolled_bound<(OCP_KN > 0)>(o.dm.mi)) {}   // (static layout: the four run-time members stay run-time values — they bound the cold loops (serial line search, the fallback of the rank-2 update), which stay rolled; the hot paths read n_ct() .. mi_ct(), and the stride ldw is a constant)
@@ -318,7 +307,7 @@ struct SqpDevice {
         // node) that holds xi = x + alpha p of its node's states and inputs in registers anyway (the NN nodes of a candidate hold each of its n variables once; the
         // parameters are node 0's), and left in LDS as pairs; the candidate's summing lane reads the pairs and runs the same two ordered chains, idx ascending.
         // Without room for the pairs (the launcher's flag) the summing lane forms the terms itself, as before.
-        constexpr bool WIDE_CT = PMPC_WIDE_TERMS >= 2 && NN > 0;
+        constexpr bool WIDE_CT = NN > 0;
         const bool wide = WIDE_CT && ls_wide;
         double* cand_box = cand_alpha + G;         // [G][n][2]   (wide only)
         const long long p0_ = now();
@@ -951,14 +940,14 @@ struct SqpDevice {
         wfence();
         wsync();
     }
-    // The same update with its rank-2 part on the LOWER TRIANGLE, dealt over all 64 lanes (PMPC_WIDE_TERMS >= 1): for the one-row-per-lane kernels with the dense
+    // The same update with its rank-2 part on the LOWER TRIANGLE, dealt over all 64 lanes: for the one-row-per-lane kernels with the dense
     // damped BFGS and a BITWISE SYMMETRIC B (the precondition of the direct tile staging, pmpc_qp_reg.hpp: no block BFGS, no hook build). Row i on lane i formed all
     // n entries of its row — n of 64 lanes at work, and every off-diagonal entry formed twice, (-Bs_i Bs_j and r_i r_j commute: the update keeps B symmetric bit for bit).
     // Here the n (n + 1) / 2 entries (i, j), i >= j, are dealt TriDeal::SLOTS per lane (10 at n = 35): loaded beside the row loads, updated by the expression of
     // bfgs_update_reg, stored to (i, j) and to (j, i) — storage stays full, the KKT staging and the residual evaluations read rows and columns as before.
     // Unchanged: the row loads and B s (lane i, columns ascending), the scalar products, the damping, the early return and the generic-division fallback.
     // No lane is switched off in the new part (clamped entries, TriDeal): nothing here narrows EXEC over live registers.
-    static constexpr bool TRI_BFGS = PMPC_WIDE_TERMS >= 1 && REG1 && HU == 0 && !POL;
+    static constexpr bool TRI_BFGS = REG1 && HU == 0 && !POL;
     __device__ __forceinline__ void bfgs_update_tri() {
         using TD = TriDeal<(NN > 0 ? NN : 1)>;
         constexpr unsigned LDW = NN + MM;
@@ -1225,7 +1214,7 @@ struct SqpDevice {
             if constexpr (POL) boxadmm_solve_reg2<NN, MM, true, true>(Hw, v.h, Aw, v.al, v.au, v.lx, v.ux, nullptr, nullptr, qs, qi, qw.x, qw.y, tr, PROF ? &cyc[PROF ? 6 : 0] : nullptr, PROF ? &cyc[PROF ? 16 : 0] : nullptr);
             else boxadmm_solve_reg2<NN, MM, true, true>(Hw, v.h, Aw, v.al, v.au, v.lx, v.ux, nullptr, nullptr, qs, qi, qw.x, qw.y, tr, PROF ? &cyc[PROF ? 6 : 0] : nullptr, PROF ? &cyc[PROF ? 16 : 0] : nullptr, jview());
             wsync();
-        } else if constexpr (REG1) { boxadmm_solve_reg<NN, MM, true, (HU == 1) || POL || PMPC_EXPERIMENT_FORCE_SYMLOWER>(   /* lower-triangle read of H: the block BFGS and a Ruiz-scaled H (D_i H_ij D_j) are not bitwise symmetric */ Hw, v.h, Aw, v.al, v.au, v.lx, v.ux, nullptr, nullptr, qs, qi, qw.x, qw.y, tr, PROF ? &cyc[PROF ? 6 : 0] : nullptr, PROF ? &cyc[PROF ? 16 : 0] : nullptr); wsync(); }
+        } else if constexpr (REG1) { boxadmm_solve_reg<NN, MM, true, (HU == 1) || POL>(   /* lower-triangle read of H: the block BFGS and a Ruiz-scaled H (D_i H_ij D_j) are not bitwise symmetric */ Hw, v.h, Aw, v.al, v.au, v.lx, v.ux, nullptr, nullptr, qs, qi, qw.x, qw.y, tr, PROF ? &cyc[PROF ? 6 : 0] : nullptr, PROF ? &cyc[PROF ? 16 : 0] : nullptr); wsync(); }
         else {
             // Solver<Problem, ADMM<...>>: the launcher sized the QP's LDS for the stacked (2n+m)-row system when qp_solver = 1
             if (RUIZ_COMPILED && __builtin_amdgcn_readfirstlane(ss.qp_solver) == 1) admm_solve(qw, n, m, Hw, ldw, v.h, Aw, ldw, v.al, v.au, v.lx, v.ux, nullptr, nullptr, qs, qi);
@@ -1294,10 +1283,6 @@ struct SqpDevice {
                 double* r = trace + (size_t)(iter - 1) * PMPC_TRACE_DOUBLES;
                 r[0] = (double)iter; r[1] = alpha_log; r[2] = primal_norm; r[3] = dual_norm; r[4] = cost_log;
                 r[5] = (double)qp_iter_last; r[6] = (double)qp_status_last; r[7] = max_violation;
-#ifdef PMPC_EXPERIMENT_WG_STAMPS   /* developer build (tests/experiments/launch_timeline.py): wall-clock stamps (100 MHz) instead of alpha / the step norms — when this iteration ended, when the workgroup started, where it ran */
-                r[1] = (double)wall_clock64(); r[2] = (double)t_start_stamp;
-                { unsigned xcc_; asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID, 0, 4)" : "=s"(xcc_)); r[3] = (double)(xcc_ & 7u); }
-#endif
             }
             if (done) { status = PMPC_SQP_SOLVED; break; }
             if (iter >= ss.max_iter) break;

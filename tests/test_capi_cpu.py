@@ -104,6 +104,21 @@ def test_product_does_not_touch_the_oracle():
                     assert bad is None, f"{os.path.join(dp, f)} reaches into the oracle: {bad.group(0)}"
 
 
+def test_no_build_option_beyond_the_documented_ones():
+    """A preprocessor conditional on a PMPC_ macro is a build option: a second product in the tree. The two that exist are PMPC_LIBM_TRANSCENDENTALS (documented
+    product option) and PMPC_BUILTIN_DEFINITIONS (structural: which translation unit defines the built-in models); no include guard starts with PMPC_. An A/B
+    switch lives on the branch that measures it."""
+    allowed = {"PMPC_LIBM_TRANSCENDENTALS", "PMPC_BUILTIN_DEFINITIONS"}
+    for base in (os.path.join("polympc_amd", "csrc"), "include"):
+        for dp, _, fs in os.walk(os.path.join(ROOT, base)):
+            for f in fs:
+                with open(os.path.join(dp, f), errors="ignore") as fh:
+                    text = fh.read()
+                for m in re.finditer(r"^[ \t]*#[ \t]*(?:if|ifdef|ifndef|elif)\b(?:\\\n|[^\n])*", text, re.M):   # the directive with its backslash-continued lines
+                    extra = set(re.findall(r"\bPMPC_\w+", m.group(0))) - allowed
+                    assert not extra, f"{os.path.join(dp, f)}:{text.count(chr(10), 0, m.start()) + 1} tests {sorted(extra)}"
+
+
 def test_workload_generator_is_deterministic():
     from polympc_amd import workloads
     a = workloads.robot_batch(8); b = workloads.robot_batch(4, first=4)

@@ -44,7 +44,7 @@ def test_two_wave_kernels_fit_half_the_register_file():
                     continue
                 model, nn, mm, flags = k
                 # (.vgpr_count is the unified count: architected registers + accumulation file)
-                if nn > 0 and nn + mm <= 64:      # one KKT row per lane: PMPC_SQP_WAVES = 2
+                if nn > 0 and nn + mm <= 64:      # one KKT row per lane: SQP_WAVES = 2
                     seen["reg1"] += 1
                     assert vgpr <= 256, f"{dn[:120]}: {vgpr} registers, two wavefronts per SIMD need <= 256"
                 elif flags & SQP_HBM and flags & SQP_TWO_WAVES:   # HBM-factor kernel, two wavefronts per SIMD

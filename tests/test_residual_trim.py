@@ -1,4 +1,4 @@
-"""The residual evaluation of boxadmm_solve_reg (pmpc_qp_reg.hpp, PMPC_RESIDUAL_TRIM): the five infinity norms of one evaluation come out of ONE
+"""The residual evaluation of boxadmm_solve_reg (pmpc_qp_reg.hpp, residuals_update): the five infinity norms of one evaluation come out of ONE
 transposed wave reduction (wave_max5, pmpc_qp.hpp) and, on the stacked workspace of the fused SQP kernels, the 56 loads of an evaluation take their
 addresses from two per-lane offsets computed once. Neither changes a bit of any residual entry — a maximum is exact and order-free — so every test is a
 comparison against the CPU restatement in the kernel's own order (PIVOT_SWEEP): x, lambda / y, iteration counts, statuses, and on the QP entry point

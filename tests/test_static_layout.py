@@ -1,4 +1,4 @@
-"""The register-resident SQP kernels with their sizes and LDS addresses as compile-time constants (PMPC_STATIC_LAYOUT, pmpc_ocp.hpp / pmpc_launch.hpp): an
+"""The register-resident SQP kernels with their sizes and LDS addresses as compile-time constants (the static layout, pmpc_ocp.hpp / pmpc_launch.hpp): an
 instantiation <NN, MM> fixes the node count K = MM / (NX + NG), and with it n, m, me, mi and the offset of every LDS array; D (with its extra row) and w, the
 two arrays sized by P, moved behind everything node-sized. No operation and no order of a sum changes, so every case is a bit-for-bit comparison with the CPU
 restatement in the kernel's own order: x, lambda, the info fields and every iteration record (and the carried filter where there is one), on every instance,

@@ -1,4 +1,4 @@
-"""CPU side of tests/test_static_layout.py (PMPC_STATIC_LAYOUT, pmpc_ocp.hpp): what the static layout of the register-resident SQP kernels must leave alone, and
+"""CPU side of tests/test_static_layout.py (the static layout, pmpc_ocp.hpp): what the static layout of the register-resident SQP kernels must leave alone, and
 what it rests on, read without a GPU.
 
 (1) The dynamic LDS bytes the launcher requests for every register grid of the built-in models (five models, every (P, S) with 3 .. 16 nodes and at most 128 KKT

@@ -1,4 +1,4 @@
-"""The phases of the fused SQP loop that PMPC_WIDE_TERMS spreads over the wavefront (pmpc_sqp.hpp): the rank-2 part of the dense damped BFGS update
+"""The phases of the fused SQP loop that are spread over the wavefront (the wide terms, pmpc_sqp.hpp): the rank-2 part of the dense damped BFGS update
 on the lower triangle of B, dealt over all 64 lanes and stored to (i, j) and (j, i) (bfgs_update_tri), and the box terms of the line search's
 violation sums formed in its node phase (step_size_selection, `wide`). Neither changes an operation or the order of a sum, so every case is a
 bit-for-bit comparison with the CPU restatement in the kernel's own order (PIVOT_SWEEP): x, lambda, the info fields and every iteration record,

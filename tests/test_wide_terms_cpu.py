@@ -1,4 +1,4 @@
-"""CPU side of tests/test_wide_terms.py (pmpc_sqp.hpp, PMPC_WIDE_TERMS): the entry <-> lane mapping of the triangle update restated from the
+"""CPU side of tests/test_wide_terms.py (pmpc_sqp.hpp, the wide terms): the entry <-> lane mapping of the triangle update restated from the
 comment that documents it (TriDeal), and the data of the GPU cases judged on the restatement — which BFGS branches and which line-search outcomes
 the instance windows reach.
 
