@@ -346,6 +346,24 @@ public:
         if (st == PMPC_OK) { m_x.swap(xo); m_lam.swap(lo); }
         return last_error() = st;
     }
+    // Newton steps on the active set of the solutions solve() left (pmpc_sqp_refine_batch; built-in OCPs on one device): primal_solution(b) /
+    // dual_solution(b) go to the KKT point of their active set, an instance whose KKT residual does not improve keeps its solution
+    // (PMPC_REFINE_REJECTED in refine_info(b).flags). act_tol: how close to a bound counts as active, the solver's eps_prim by default.
+    // sens_idx / dz: variables pinned by an equality bound and the derivative of the solution with respect to their value (B * nsens * VAR_SIZE).
+    pmpc_status refine(int steps = 3, double act_tol = -1.0, const std::vector<int>& sens_idx = std::vector<int>(), std::vector<double>* dz = nullptr) noexcept {
+        if (!m_multi.empty() || (!sens_idx.empty() && !dz)) return last_error() = PMPC_ERR_INVALID_ARGUMENT;
+        pmpc_context* ctx = context();
+        if (!ctx) return last_error();
+        const std::vector<double> mp = problem.model_params();
+        m_refine_info.resize(B);
+        if (dz) dz->assign((size_t)B * sens_idx.size() * VAR_SIZE, 0.0);
+        return last_error() = pmpc_sqp_refine_batch(ctx, device_binding<OCP>::model_id, OCP::POLY_ORDER, OCP::NUM_SEGMENTS, problem.t_start, problem.t_stop,
+                                                    mp.empty() ? nullptr : mp.data(), (int)mp.size(), B, m_p.data(), m_lbx.data(), m_ubx.data(),
+                                                    (NUM_INEQ > 0) ? m_lbg.data() : nullptr, (NUM_INEQ > 0) ? m_ubg.data() : nullptr, steps,
+                                                    act_tol < 0.0 ? m_settings.eps_prim : act_tol, m_x.data(), m_lam.data(), m_refine_info.data(),
+                                                    (int)sens_idx.size(), sens_idx.empty() ? nullptr : sens_idx.data(), dz ? dz->data() : nullptr);
+    }
+    const pmpc_refine_info& refine_info(int b) const noexcept { return m_refine_info[b]; }
     // the same solve with the batch in contiguous shards [k B / N, (k+1) B / N) over the N contexts of set_devices(), one host thread per shard
     pmpc_status solve_sharded() noexcept {
         // per-instance device state of ONE context cannot follow the shards: no iteration records, and the filter line search runs with a
@@ -391,6 +409,7 @@ public:
     OCP problem;
     int B;
     std::vector<double> m_x, m_lam, m_lbx, m_ubx, m_lbg, m_ubg, m_p;
+    std::vector<pmpc_refine_info> m_refine_info;
     std::vector<pmpc_sqp_info> m_info;
     std::vector<double> m_trace; int m_trace_capacity = 0;
     std::vector<std::unique_ptr<ContextHolder>> m_multi;   // set_devices(): one context per shard
@@ -471,6 +490,16 @@ public:
         m_primal_norm = i.primal_norm; m_dual_norm = i.dual_norm; m_max_violation = i.max_violation; m_cost = i.cost;
     }
     void solve(const nlp_variable_t& x_guess, const nlp_dual_t& lam_guess) noexcept { m_x = x_guess; m_lam = lam_guess; solve(); }
+    /** not in the reference: Newton steps on the active set of the solution solve() left (BatchSolver::refine); false when the call was refused or
+     *  the KKT residual did not improve — the solution then is the one solve() returned. refine_info() has the residuals before and after. */
+    bool refine(int steps = 3, double act_tol = -1.0) noexcept {
+        if (m_batch.refine(steps, act_tol) != PMPC_OK) return false;
+        if (m_batch.refine_info(0).flags & PMPC_REFINE_REJECTED) return false;
+        std::copy(m_batch.primal_solution(0), m_batch.primal_solution(0) + VAR_SIZE, m_x.data());
+        std::copy(m_batch.dual_solution(0), m_batch.dual_solution(0) + OCP::DUAL_SIZE, m_lam.data());
+        return true;
+    }
+    const pmpc_refine_info& refine_info() const noexcept { return m_batch.refine_info(0); }
     // copies (the reference's SQPBase is copyable): `filter` below is a reference into this object's own m_batch — a memberwise copy would leave
     // the copy's reference on the ORIGINAL's filter, and a reference member deletes the implicit assignment
     Solver(const Solver& o)
@@ -785,6 +814,17 @@ public:
         return last_error() = pmpc_mpc_batch_update(m_batch, nd > 0 ? m_p.data() : nullptr, m_lbx.data(), m_ubx.data(), num_ineq > 0 ? m_lbg.data() : nullptr,
                                                     num_ineq > 0 ? m_ubg.data() : nullptr);
     }
+    // Newton steps on the active set of every controller's iterate, in place on the device (pmpc_mpc_batch_refine; a built-in OCP only — a
+    // registered one is refused with PMPC_ERR_UNKNOWN_MODEL): the SQP-tolerance answer of step() taken to the KKT point of its active set, an
+    // instance that does not improve keeps its iterate (PMPC_REFINE_REJECTED in refine_info(b).flags). gain receives B * nu * nx values,
+    // gain[(b * nu + c) * nx + j] = d u_c(t_start) / d x0_j: the first-order feedback of controller b around its solution. act_tol: how close
+    // to a bound counts as active — the solver's eps_prim by default.
+    pmpc_status refine(std::vector<double>& gain, int steps = 3, double act_tol = -1.0) noexcept {
+        if (!m_batch) return PMPC_ERR_INVALID_ARGUMENT;
+        gain.resize((size_t)B * nu * nx); m_refine_info.resize(B);
+        return last_error() = pmpc_mpc_batch_refine(m_batch, steps, act_tol < 0.0 ? m_settings.eps_prim : act_tol, gain.data(), m_refine_info.data());
+    }
+    const pmpc_refine_info& refine_info(int b) const noexcept { return m_refine_info[b]; }
     const pmpc_sqp_info& info(int b) const noexcept { return m_info[b]; }
     // current primal solution of every controller (B * var_size), downloaded on demand
     pmpc_status solution(std::vector<double>& x) noexcept {
@@ -836,6 +876,7 @@ private:
     OCP problem; int B;
     std::vector<double> m_lbx, m_ubx, m_lbg, m_ubg, m_p, m_plant_d, m_iterate;
     std::vector<pmpc_sqp_info> m_info;
+    std::vector<pmpc_refine_info> m_refine_info;
     sqp_settings_t m_settings; qp_solver_settings_t m_qp_settings;
     pmpc_mpc_batch* m_batch{nullptr};
     int m_dispatch_mode{0}, m_iter_weight{default_iter_weight};

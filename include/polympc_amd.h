@@ -177,8 +177,8 @@ typedef enum {
  * enum values, a trace pointer with a capacity < 1 — with PMPC_ERR_INVALID_ARGUMENT, but a garbage pointer cannot be detected). */
 #define PMPC_ABI_VERSION 4
 int pmpc_abi_version(void);
-/* sizeof of the library's own struct: which = 0 pmpc_qp_settings, 1 pmpc_qp_info, 2 pmpc_sqp_settings, 3 pmpc_sqp_info, 4 pmpc_plant_settings;
- * 0 for anything else */
+/* sizeof of the library's own struct: which = 0 pmpc_qp_settings, 1 pmpc_qp_info, 2 pmpc_sqp_settings, 3 pmpc_sqp_info, 4 pmpc_plant_settings,
+ * 6 pmpc_polish_info, 7 pmpc_refine_info; 0 for anything else (5 is not assigned: hosts of the plant entries probe it as the first unknown id) */
 unsigned long pmpc_struct_size(int which);
 const char* pmpc_version(void);
 const char* pmpc_status_string(pmpc_status s);
@@ -615,6 +615,113 @@ pmpc_status pmpc_nlp_solve_batch_user(pmpc_context* ctx, pmpc_nlp_dev_fn fn, con
                                       const double* x_guess, const double* lam_guess, const double* d, const double* lbx, const double* ubx,
                                       const double* lbg, const double* ubg, const pmpc_sqp_settings* sqp_settings,
                                       const pmpc_qp_settings* qp_settings, double* x, double* lam, pmpc_sqp_info* info);
+
+/* ---- active-set KKT solve of a QP ("polish") ---------------------------------------------------------------------------------
+ * min 1/2 p'Hp + h'p, Alb <= Ap <= Aub, xlb <= p <= xub in the layouts of pmpc_qp_boxadmm_solve_batch, solved DIRECTLY on a fixed active set: the
+ * step that turns an ADMM-tolerance answer into the stationary point of its active set (OSQP's polish), and, with more right-hand sides, the
+ * derivative of that point with respect to variables that are pinned by an equality bound. Dimensions only, no model id. Only the LOWER triangle
+ * of H is read: Hs_ij = H[max(i,j), min(i,j)]. One wavefront per instance, the system in LDS. Every quantity below is one fp64 operation per
+ * written operation, in the written order, so a result is the same bits whatever the batch or the launch looks like.
+ *
+ * 1. Active set, at the point p_in (NULL = zeros). For variable i with lo = xlb_i, hi = xub_i, v = p_in_i; for row r with lo = Alb_r, hi = Aub_r,
+ *    v = 0, then v = v + A_rj * p_in_j for j ascending:
+ *      eq = (hi - lo < 1e-4)   (the EQUALITY rule of qp_base.hpp:195-222);   dl = v - lo;   du = hi - v;
+ *      al = lo finite and dl <= act_tol;   au = hi finite and du <= act_tol   (an infinite bound never activates; a NaN compares false)
+ *      mask = 3 if eq;  else 2 if au and (not al or du < dl);  else 1 if al;  else 0     (0 free, 1 lower, 2 upper, 3 equality)
+ *      target t = hi if (mask == 2, or mask == 3 and du < dl), else lo                    (the nearer bound, a tie goes to the lower one)
+ *    frozen != 0: the masks are READ instead (masks & 3), and only the targets are computed, by the last rule.
+ *    masks: B * (m + n) signed chars in the order of y, [rows (m) | variables (n)]; written when frozen == 0.
+ * 2. System of N = n + m rows, unknowns z = [p (n) | y (m)], K = [[Hs, A'], [A, 0]]: the row and the column of every ACTIVE variable and of every
+ *    INACTIVE row are replaced by a unit row and column. Right-hand side, with a_1 < a_2 < ... the active variables:
+ *      free variable i:   b = -h_i;  b = b - Hs_{i a} * t_a for a ascending          active variable i:  b = t_i
+ *      active row r:      b = t_r;   b = b - A_{r a} * t_a for a ascending          inactive row:       b = 0
+ * 3. Gaussian elimination with partial pivoting on [K | b | sensitivity columns]. Step k = 0 .. N-1: key_r = |K_rk| (a NaN counts as +inf) for
+ *    r >= k; the pivot row is the FIRST r with the largest key; a pivot that is zero or not finite ends the instance with PMPC_POLISH_SINGULAR:
+ *    p, y and dP of that instance then keep what they held (masks and info are written). Rows k and the pivot row are exchanged; for every row r > k:
+ *    l = K_rk / K_kk, then K_rc = K_rc - l * K_kc for every column c > k and every right-hand side. Back substitution, k = N-1 .. 0:
+ *    z_k = b_k / K_kk, then b_r = b_r - K_rk * z_k for every r < k.
+ * 4. Outputs: p = z[0..n); y[r] = z[n + r] on active rows and 0 on inactive ones; y[m + i] = 0 on free variables and on active ones
+ *      g = 0;  g = g + Hs_ij * p_j (j ascending);  g = g + h_i;  s = 0;  s = s + A_ri * y_r (r ascending);  g = g + s;  y[m + i] = -g
+ *    (the sign convention of res_dual, qp_base.hpp:240-252: Hp + h + A'y_A + y_box = 0, a multiplier is <= 0 at a lower and >= 0 at an upper bound).
+ *    info.res_in: the KKT residual of (p_in, y_in) on this active set — the largest of |g_i| on free variables (g as above from p_in and the
+ *    y_in of ACTIVE rows; y_in NULL = zeros), |v_r - t_r| on active rows and |p_in_i - t_i| on active variables; a NaN term counts as +inf.
+ *    info.pivot_min / pivot_max: the smallest and largest |pivot| (their ratio estimates the conditioning; pivot_min = 0 when singular).
+ * 5. Sensitivities: sens_idx, nsens <= PMPC_POLISH_MAX_SENS variable indices shared by the batch — a HOST array in both forms (it travels as a
+ *    kernel argument). Column q, for j = sens_idx[q] with mask 3, is the right-hand side -K_full[:, j] on the rows that step 2 kept (free
+ *    variables: -Hs_ij, active rows: -A_rj), 1 on row j itself and 0 on every other replaced row; its solution's first n entries are
+ *    dP[(b * nsens + q) * n ..] = dp / dt_j. An index outside 0 .. n-1 or whose mask is not 3 gives a column of zeros and
+ *    PMPC_POLISH_SENS_INACTIVE.
+ * Flags: PMPC_POLISH_SIGN — a multiplier y > 0 on mask 1 or y < 0 on mask 2 (row or variable); PMPC_POLISH_INFEASIBLE — at p a bound that is not
+ * the active one is violated by more than act_tol (lo - v > act_tol unless mask is 1 or 3, v - hi > act_tol unless mask is 2 or 3; v = p_i, or A p
+ * summed as in step 1); PMPC_POLISH_NONFINITE — p or y holds a non-finite value.
+ * Size: 8 N (N + 1 + nsens) + 20 N bytes of LDS per instance must fit the device's opt-in maximum of dynamic LDS (160 KiB on gfx950: every system
+ * up to 128 rows with PMPC_POLISH_MAX_SENS columns); PMPC_ERR_UNSUPPORTED_SIZE beyond. Every refusal is answered before any device call and leaves
+ * the outputs untouched — PMPC_ERR_INVALID_ARGUMENT: a NULL ctx, H, h, xlb, xub, masks, p, y or info; B < 0, n < 1, m < 0; m > 0 without A, Alb or
+ * Aub; act_tol negative or NaN; nsens outside 0 .. PMPC_POLISH_MAX_SENS, or > 0 without sens_idx or dP. B == 0: nothing is done.
+ * The _dev form takes device pointers (sens_idx excepted) and is asynchronous on the context's stream; the host form copies in (p, y and dP
+ * included, so that a singular instance keeps its values), solves, copies out and synchronises. New entry points: PMPC_ABI_VERSION stays. */
+typedef struct {
+    int active_vars, active_rows;   /* variables / rows with a mask != 0 */
+    int flags;                      /* PMPC_POLISH_* */
+    int reserved;                   /* 0 */
+    double res_in, pivot_min, pivot_max;
+} pmpc_polish_info;                 /* pmpc_struct_size(6) */
+#define PMPC_POLISH_SINGULAR 1
+#define PMPC_POLISH_SIGN 2
+#define PMPC_POLISH_INFEASIBLE 4
+#define PMPC_POLISH_NONFINITE 8
+#define PMPC_POLISH_SENS_INACTIVE 16
+#define PMPC_POLISH_MAX_SENS 16
+pmpc_status pmpc_qp_polish_batch_dev(pmpc_context* ctx, int B, int n, int m, const double* H, const double* h, const double* A, const double* Alb,
+                                     const double* Aub, const double* xlb, const double* xub, const double* p_in, const double* y_in, double act_tol,
+                                     int frozen, signed char* masks, int nsens, const int* sens_idx, double* p, double* y, pmpc_polish_info* info,
+                                     double* dP);
+pmpc_status pmpc_qp_polish_batch(pmpc_context* ctx, int B, int n, int m, const double* H, const double* h, const double* A, const double* Alb,
+                                 const double* Aub, const double* xlb, const double* xub, const double* p_in, const double* y_in, double act_tol,
+                                 int frozen, signed char* masks, int nsens, const int* sens_idx, double* p, double* y, pmpc_polish_info* info,
+                                 double* dP);
+
+/* ---- refinement of an SQP solution on its active set, and its sensitivities -------------------------------------------------------------
+ * The solver returns SQP-tolerance answers (eps_prim / eps_dual, ADMM inside). These entries take such an answer of a BUILT-IN OCP to the KKT
+ * point of its own active set with full Newton steps — each one polish (above) of the QP of the exact linearisation — and differentiate that
+ * point with respect to variables pinned by an equality bound (the measured state of an MPC problem). x (B * n) and lam (B * (m + n)) are refined
+ * IN PLACE. For k = 0 .. steps:
+ *   1. linearise at (x, lam): the kernel of pmpc_ocp_linearise_batch on device buffers (exact Lagrangian Hessian);
+ *   2. the QP: H = lag_hess, h = cost_grad, A = jac; Alb = Aub = -c on the equality rows, lbg - g and ubg - g on the path rows; xlb = lbx - x,
+ *      xub = ubx - x; p_in = zeros, y_in = lam;
+ *   3. k = 0 decides the active set with act_tol, later steps reuse its masks (frozen);
+ *   4. r_k = res_in of the polish: the KKT residual of (x, lam) on that active set;
+ *   5. k < steps: x = x + p, lam = y (the QP's multipliers, not an increment); an instance whose system is singular at step k keeps x and lam there;
+ *   6. after k = steps: accepted if steps == 0, or r_steps is finite and r_steps < r_0; otherwise x and lam get their input values back, bit for
+ *      bit, and PMPC_REFINE_REJECTED is set (the iterate was not near a KKT point of its geometric active set: the operation measures, it does
+ *      not assume);
+ *   7. dz (B * nsens * n; nsens, sens_idx as for the polish: a HOST array in both forms) = d x / d (the equality value of variable sens_idx[q]),
+ *      solved at the LAST linearisation for accepted instances, zeros for rejected ones and for a system singular there.
+ * info: steps (the Newton steps taken), the active counts of step 0, flags = the OR of the PMPC_POLISH_* flags of every step | PMPC_REFINE_REJECTED,
+ * r_0 and r_last = r_steps. Refused before any device call, outputs untouched — PMPC_ERR_INVALID_ARGUMENT: a NULL ctx, lbx, ubx, x, lam or info; B < 0;
+ * d NULL with ND > 0; lbg / ubg NULL with NG > 0; steps outside 0 .. PMPC_REFINE_MAX_STEPS; act_tol negative or NaN; nsens outside
+ * 0 .. PMPC_POLISH_MAX_SENS, or > 0 without sens_idx or dz; PMPC_ERR_UNKNOWN_MODEL; PMPC_ERR_UNSUPPORTED_SIZE for a grid whose KKT system exceeds
+ * the polish's LDS limit (every grid up to 128 KKT rows is served; the kite stand-in is not). B == 0: nothing is done. The _dev form takes device
+ * pointers and is asynchronous on the context's stream (the context's HBM workspace holds the linearisation and the QP between the launches);
+ * the host form copies in, refines, copies out and synchronises. New entry points: PMPC_ABI_VERSION stays. */
+typedef struct {
+    int steps, active_vars, active_rows;
+    int flags;            /* PMPC_POLISH_* of every step | PMPC_REFINE_REJECTED */
+    double r_0, r_last;
+} pmpc_refine_info;       /* pmpc_struct_size(7) */
+#define PMPC_REFINE_REJECTED 32
+#define PMPC_REFINE_MAX_STEPS 8
+pmpc_status pmpc_sqp_refine_batch_dev(pmpc_context* ctx, int model, int P, int S, double t0, double tf, const double* mparams, int n_mparams, int B,
+                                      const double* d, const double* lbx, const double* ubx, const double* lbg, const double* ubg, int steps,
+                                      double act_tol, double* x, double* lam, pmpc_refine_info* info, int nsens, const int* sens_idx, double* dz);
+pmpc_status pmpc_sqp_refine_batch(pmpc_context* ctx, int model, int P, int S, double t0, double tf, const double* mparams, int n_mparams, int B,
+                                  const double* d, const double* lbx, const double* ubx, const double* lbg, const double* ubg, int steps,
+                                  double act_tol, double* x, double* lam, pmpc_refine_info* info, int nsens, const int* sens_idx, double* dz);
+/* On an opaque batch of a built-in OCP: refines the batch's iterate in place with its own bounds and static parameters; sens_idx = the last nx
+ * entries of the x block (the pinned measured state). gain (host, B * nu * nx, may be NULL): gain[(b * nu + c) * nx + j] = d u_c(t_start) / d x0_j,
+ * the rows of dz at the last node of the u block — the first-order feedback of the controller around its solution; zeros for a rejected instance.
+ * info (host, B, may be NULL). A registered OCP's batch has no linearisation entry: PMPC_ERR_UNKNOWN_MODEL. The call synchronises. */
+pmpc_status pmpc_mpc_batch_refine(pmpc_mpc_batch* batch, int steps, double act_tol, double* gain, pmpc_refine_info* info);
 
 #ifdef __cplusplus
 }

@@ -13,4 +13,6 @@ from .capi import (  # noqa: F401
     QP_SOLVED, QP_MAX_ITER_EXCEEDED, SQP_SOLVED, SQP_MAX_ITER_EXCEEDED, EXPORTED_SYMBOLS,
     NLP_CONSTRAINED_ROSENBROCK, NLP_ROSENBROCK, NLP_SIMPLE, NLP_HS071, StatusError, UserNLP, nlp_dims, UserOCP, MPCBatch,
     PlantSettings, plant_settings_default,
+    POLISH_INFO_DTYPE, POLISH_SINGULAR, POLISH_SIGN, POLISH_INFEASIBLE, POLISH_NONFINITE, POLISH_SENS_INACTIVE, POLISH_MAX_SENS,
+    REFINE_INFO_DTYPE, REFINE_REJECTED, REFINE_MAX_STEPS,
 )

@@ -69,6 +69,17 @@ SQP_INFO_DTYPE = np.dtype([("iter", "i4"), ("qp_solver_iter", "i4"), ("status", 
                            ("primal_norm", "f8"), ("dual_norm", "f8"), ("max_violation", "f8"), ("cost", "f8")])
 assert QP_INFO_DTYPE.itemsize == C.sizeof(QPInfo) == 40 and SQP_INFO_DTYPE.itemsize == C.sizeof(SQPInfo) == 48
 
+# pmpc_polish_info (pmpc_struct_size(6)) and the PMPC_POLISH_* flags of the active-set KKT solve
+POLISH_INFO_DTYPE = np.dtype([("active_vars", "i4"), ("active_rows", "i4"), ("flags", "i4"), ("reserved", "i4"),
+                              ("res_in", "f8"), ("pivot_min", "f8"), ("pivot_max", "f8")])
+assert POLISH_INFO_DTYPE.itemsize == 40
+POLISH_SINGULAR, POLISH_SIGN, POLISH_INFEASIBLE, POLISH_NONFINITE, POLISH_SENS_INACTIVE = 1, 2, 4, 8, 16
+POLISH_MAX_SENS = 16
+# pmpc_refine_info (pmpc_struct_size(7)); its flags: the PMPC_POLISH_* of every step | REFINE_REJECTED
+REFINE_INFO_DTYPE = np.dtype([("steps", "i4"), ("active_vars", "i4"), ("active_rows", "i4"), ("flags", "i4"), ("r_0", "f8"), ("r_last", "f8")])
+assert REFINE_INFO_DTYPE.itemsize == 32
+REFINE_REJECTED, REFINE_MAX_STEPS = 32, 8
+
 # ---------------------------------------------------------------------------------------------------------------------
 # Every function include/polympc_amd.h declares, in the header's order: name -> (restype, argtypes). The one statement of the C signatures on the
 # Python side: lib() installs it on the loaded library, tests/test_capi_cpu.py compares all of it with the header. double* / float* and the
@@ -99,6 +110,8 @@ _NLP = _I, [_V, _I, _I] + _SQP_IN + _SQP_TAIL                             # ctx,
 _TRAJ_SAMPLE = _I, _TRAJ_HEAD + [_I, _I, _D, _D, _P, _I, _P, _I, _P, _P]  # P, S, t0, tf, x, K, t, t_per_instance, xs, us
 _TRAJ_REGRID = _I, _TRAJ_HEAD + [_I] * 4 + [_D, _D, _P, _P]               # P, S, P2, S2, t0, tf, x_src, x_dst
 _PLANT = _I, [_V, _I, _P, _I, _I, _I, _D, _D] + _PLANT_TAIL               # ctx, model, mparams, n_mparams, P, S, t0, tf, ...
+_POLISH = _I, _QP_HEAD + [_P] * 9 + [_D, _I, _V, _I, _V, _P, _P, _V, _P]     # H .. xub, p_in, y_in, act_tol, frozen, masks, nsens, sens_idx, p, y, info, dP
+_REFINE = _I, [_V] + _OCP_GRID + [_I] + [_P] * 5 + [_I, _D, _P, _P, _V, _I, _V, _P]   # ..., B, d, lbx, ubx, lbg, ubg, steps, act_tol, x, lam, info, nsens, sens_idx, dz
 _PLANT_USER = _I, _USER_OCP_HEAD + [_I] * 6 + [_D, _D] + _PLANT_TAIL      # ctx, fn, model, nx, nu, np, nd, P, S, t0, tf, ...
 
 SIGNATURES = {
@@ -184,6 +197,13 @@ SIGNATURES = {
     "pmpc_nlp_solve_batch": _NLP,
     "pmpc_nlp_solve_batch_dev": _NLP,
     "pmpc_nlp_solve_batch_user": (_I, [_V, _V, _V] + [_I] * 5 + _SQP_IN + _SQP_TAIL),   # ctx, fn, model, nx, ne, ni, np, B, ...
+    # ---- active-set KKT solve of a QP
+    "pmpc_qp_polish_batch_dev": _POLISH,
+    "pmpc_qp_polish_batch": _POLISH,
+    # ---- refinement of an SQP solution on its active set
+    "pmpc_sqp_refine_batch_dev": _REFINE,
+    "pmpc_sqp_refine_batch": _REFINE,
+    "pmpc_mpc_batch_refine": (_I, [_V, _I, _D, _P, _V]),
 }
 EXPORTED_SYMBOLS = list(SIGNATURES)
 
@@ -516,6 +536,14 @@ class MPCBatch:
         """pmpc_mpc_batch_shift: move the batch's iterate (duals: and its multipliers) forward by dt; the next step starts from it"""
         _check_status(lib().pmpc_mpc_batch_shift(self._batch, float(dt), 1 if duals else 0))
 
+    def refine(self, steps=3, act_tol=1e-3, want_gain=True):
+        """pmpc_mpc_batch_refine: Newton steps on the active set of the batch's iterate, in place (a built-in OCP's batch only)
+        -> gain (B, nu, nx) = d u(t_start) / d x0 (None unless wanted; zeros for a rejected instance), info (REFINE_INFO_DTYPE)"""
+        gain = np.zeros((self.B, self.dims["nu"], self.dims["nx"])) if want_gain else None
+        info = np.zeros(self.B, dtype=REFINE_INFO_DTYPE)
+        _check_status(lib().pmpc_mpc_batch_refine(self._batch, int(steps), float(act_tol), _h(gain)[1], C.c_void_p(info.ctypes.data)))
+        return gain, info
+
     def set_plant(self, settings=None, d_plant=None):
         """pmpc_mpc_batch_set_plant: the plant of rollout() — settings (default: RK4, 1 substep, zero-order hold) and the plant's own static
         parameters (B, nd), None = the controller's; a registered OCP's batch passes its pmpc_user_plant_dev_<name>"""
@@ -636,6 +664,64 @@ class Context:
     def qp_solve_batch_dev(self, B, n, m, H, h, A, Alb, Aub, xlb, xub, x, y, info, settings, x0=None, y0=None):
         _check(lib().pmpc_qp_boxadmm_solve_batch_dev(self._ctx, B, n, m, _d(H), _d(h), _d(A), _d(Alb), _d(Aub), _d(xlb), _d(xub),
                                                      _d(x0), _d(y0), C.byref(settings), _d(x), _d(y), C.c_void_p(info.data_ptr())))
+
+    # ------------------------------------------------------------------ active-set KKT solve of a QP (pmpc_qp_polish_*)
+    def qp_polish(self, H, h, A, Alb, Aub, xlb, xub, p_in=None, y_in=None, act_tol=1e-6, masks=None, sens_idx=None, out=None):
+        """pmpc_qp_polish_batch (host buffers, the layout of qp_solve_batch): the KKT point of the active set decided at p_in (None: zeros) with
+        act_tol, or of the given masks (B, m + n) int8 (frozen mode). sens_idx: variable indices with an equality bound whose sensitivities are
+        wanted. out: dict(p, y, dP) of arrays to start from (a singular instance keeps them; default zeros)
+        -> dict(p (B, n), y (B, m + n), masks (B, m + n) int8, info (POLISH_INFO_DTYPE), dP (B, nsens, n))"""
+        hk, hp = _h(h); B, n = hk.shape
+        Hk, Hp = _h(H); Ak, Ap = _h(A); albk, albp = _h(Alb); aubk, aubp = _h(Aub); xlk, xlp = _h(xlb); xuk, xup = _h(xub)
+        m = albk.shape[1] if albk is not None and albk.ndim == 2 else 0
+        pk, pp = _h(p_in); yk, yp = _h(y_in)
+        sens = np.ascontiguousarray([] if sens_idx is None else sens_idx, dtype=np.int32); ns = int(sens.size)
+        frozen = masks is not None
+        mk = np.array(masks, dtype=np.int8, order="C").reshape(B, m + n) if frozen else np.zeros((B, m + n), dtype=np.int8)
+        out = out or {}
+        p = np.array(out.get("p", np.zeros((B, n))), dtype=np.float64, order="C").reshape(B, n)
+        y = np.array(out.get("y", np.zeros((B, m + n))), dtype=np.float64, order="C").reshape(B, m + n)
+        dP = np.array(out.get("dP", np.zeros((B, ns, n))), dtype=np.float64, order="C").reshape(B, ns, n)
+        info = np.zeros(B, dtype=POLISH_INFO_DTYPE)
+        P_ = C.POINTER(C.c_double)
+        _check_status(lib().pmpc_qp_polish_batch(self._ctx, B, n, m, Hp, hp, Ap, albp, aubp, xlp, xup, pp, yp, float(act_tol), 1 if frozen else 0,
+                                                 C.c_void_p(mk.ctypes.data), ns, C.c_void_p(sens.ctypes.data) if ns else None, p.ctypes.data_as(P_),
+                                                 y.ctypes.data_as(P_), C.c_void_p(info.ctypes.data), dP.ctypes.data_as(P_) if ns else None))
+        return dict(p=p, y=y, masks=mk, info=info, dP=dP)
+
+    def qp_polish_dev(self, B, n, m, H, h, A, Alb, Aub, xlb, xub, masks, p, y, info, p_in=None, y_in=None, act_tol=1e-6, frozen=False, sens_idx=None,
+                      dP=None):
+        """pmpc_qp_polish_batch_dev on torch CUDA tensors (masks int8 (B, m + n), info uint8 of B * 40 bytes; sens_idx: a host sequence of ints);
+        asynchronous on the context's stream"""
+        sens = np.ascontiguousarray([] if sens_idx is None else sens_idx, dtype=np.int32); ns = int(sens.size)
+        _check_status(lib().pmpc_qp_polish_batch_dev(self._ctx, int(B), int(n), int(m), _d(H), _d(h), _d(A), _d(Alb), _d(Aub), _d(xlb), _d(xub), _d(p_in),
+                                                     _d(y_in), float(act_tol), 1 if frozen else 0, _dv(masks), ns,
+                                                     C.c_void_p(sens.ctypes.data) if ns else None, _d(p), _d(y), _dv(info), _d(dP)))
+
+    # ------------------------------------------------------------------ refinement of an SQP solution (pmpc_sqp_refine_*)
+    def sqp_refine(self, model, P, S, t0, tf, x, lam, d, lbx, ubx, lbg=None, ubg=None, steps=3, act_tol=1e-3, sens_idx=None, mparams=None):
+        """pmpc_sqp_refine_batch (host buffers): x (B, n), lam (B, m + n) of a solve taken to the KKT point of their active set
+        -> x, lam (new arrays), info (REFINE_INFO_DTYPE), dz (B, nsens, n): d x / d (the equality value of each variable of sens_idx).
+        act_tol defaults to the solver's eps_prim: a bound the solve left that close counts as active"""
+        x = np.array(np.atleast_2d(x), dtype=np.float64, order="C"); lam = np.array(np.atleast_2d(lam), dtype=np.float64, order="C")
+        B, n = x.shape
+        sens = np.ascontiguousarray([] if sens_idx is None else sens_idx, dtype=np.int32); ns = int(sens.size)
+        dz = np.zeros((B, ns, n)); info = np.zeros(B, dtype=REFINE_INFO_DTYPE)
+        keep = [_h(a) for a in (mparams, d, lbx, ubx, lbg, ubg)]
+        P_ = C.POINTER(C.c_double)
+        _check_status(lib().pmpc_sqp_refine_batch(self._ctx, int(model), int(P), int(S), float(t0), float(tf), keep[0][1], 0 if keep[0][0] is None else len(keep[0][0]),
+                                                  B, *[k[1] for k in keep[1:]], int(steps), float(act_tol), x.ctypes.data_as(P_), lam.ctypes.data_as(P_),
+                                                  C.c_void_p(info.ctypes.data), ns, C.c_void_p(sens.ctypes.data) if ns else None, dz.ctypes.data_as(P_) if ns else None))
+        return x, lam, info, dz
+
+    def sqp_refine_dev(self, model, P, S, t0, tf, B, x, lam, info, d, lbx, ubx, lbg=None, ubg=None, steps=3, act_tol=1e-3, sens_idx=None, dz=None, mparams=None):
+        """pmpc_sqp_refine_batch_dev on torch CUDA tensors, x and lam in place (info: uint8 of B * 32 bytes; sens_idx: a host sequence of ints);
+        asynchronous on the context's stream"""
+        mk, mp = _h(mparams)
+        sens = np.ascontiguousarray([] if sens_idx is None else sens_idx, dtype=np.int32); ns = int(sens.size)
+        _check_status(lib().pmpc_sqp_refine_batch_dev(self._ctx, int(model), int(P), int(S), float(t0), float(tf), mp, 0 if mk is None else len(mk), int(B), _d(d),
+                                                      _d(lbx), _d(ubx), _d(lbg), _d(ubg), int(steps), float(act_tol), _d(x), _d(lam), _dv(info), ns,
+                                                      C.c_void_p(sens.ctypes.data) if ns else None, _d(dz)))
 
     # ------------------------------------------------------------------ collocation assembly (host buffers)
     def ocp_linearise_batch(self, model, P, S, t0, tf, var, d, lam=None, mparams=None):

@@ -57,6 +57,8 @@ unsigned long pmpc_struct_size(int which) {
         case 2: return (unsigned long)sizeof(pmpc_sqp_settings);
         case 3: return (unsigned long)sizeof(pmpc_sqp_info);
         case 4: return (unsigned long)sizeof(pmpc_plant_settings);
+        case 7: return (unsigned long)sizeof(pmpc_refine_info);
+        case 6: return (unsigned long)sizeof(pmpc_polish_info);   // (5 stays unassigned: tests/test_plant_cpu.py pins it as the first unknown id)
     }
     return 0;
 }
@@ -499,6 +501,35 @@ pmpc_status pmpc_mpc_batch_solution(pmpc_mpc_batch* h, double* x, double* lam) {
     if (x) HIPCHK(hipMemcpyAsync(x, h->x, (size_t)h->B * h->z.n * sizeof(double), hipMemcpyDeviceToHost, h->ctx->stream));
     if (lam) HIPCHK(hipMemcpyAsync(lam, h->lam, (size_t)h->B * (h->z.n + h->z.m) * sizeof(double), hipMemcpyDeviceToHost, h->ctx->stream));
     HIPCHK(hipStreamSynchronize(h->ctx->stream));
+    return PMPC_OK;
+}
+pmpc_status pmpc_mpc_batch_refine(pmpc_mpc_batch* h, int steps, double act_tol, double* gain, pmpc_refine_info* info) {
+    if (!h || steps < 0 || steps > PMPC_REFINE_MAX_STEPS || !(act_tol >= 0.0)) return PMPC_ERR_INVALID_ARGUMENT;
+    if (h->solve.fn) return PMPC_ERR_UNKNOWN_MODEL;   // a registered OCP has no linearisation entry
+    pmpc_context* ctx = h->ctx;
+    const DevSolver& sv = h->solve;
+    const OcpSizes& z = h->z;
+    const int nn = sv.P * sv.S + 1, nx = z.nx, nu = z.nu, n = z.n, B = h->B;
+    if (nx > PMPC_POLISH_MAX_SENS) return PMPC_ERR_UNSUPPORTED_SIZE;
+    int sens[PMPC_POLISH_MAX_SENS];
+    for (int j = 0; j < nx; ++j) sens[j] = nx * nn - nx + j;
+    HIPCHK(hipSetDevice(ctx->device));
+    // (slots of the QP range: no host wrapper is live around a batch call, and the refinement below takes none)
+    void *dzv = nullptr, *infov = nullptr;
+    pmpc_status st = ensure_scratch(ctx, SLOT_QP_X, (size_t)B * nx * n * sizeof(double), &dzv);
+    if (st == PMPC_OK) st = ensure_scratch(ctx, SLOT_QP_INFO, (size_t)B * sizeof(pmpc_refine_info), &infov);
+    if (st != PMPC_OK) return st;
+    st = pmpc_sqp_refine_batch_dev(ctx, sv.model, sv.P, sv.S, sv.t0, sv.tf, sv.mparams, sv.n_mparams, B, h->d, h->lbx, h->ubx, h->lbg, h->ubg, steps, act_tol,
+                                   h->x, h->lam, (pmpc_refine_info*)infov, nx, sens, (double*)dzv);
+    if (st != PMPC_OK) return st;
+    std::vector<double> dz(gain ? (size_t)B * nx * n : 0);
+    if (gain) HIPCHK(hipMemcpyAsync(dz.data(), dzv, dz.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (info) HIPCHK(hipMemcpyAsync(info, infov, (size_t)B * sizeof(pmpc_refine_info), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    if (gain)
+        for (int b = 0; b < B; ++b)
+            for (int c = 0; c < nu; ++c)
+                for (int j = 0; j < nx; ++j) gain[((size_t)b * nu + c) * nx + j] = dz[((size_t)b * nx + j) * n + (size_t)nx * nn + (size_t)nu * (nn - 1) + c];
     return PMPC_OK;
 }
 pmpc_status pmpc_mpc_batch_update(pmpc_mpc_batch* h, const double* d, const double* lbx, const double* ubx, const double* lbg, const double* ubg) {

@@ -12,6 +12,11 @@ template <class Model> pmpc_status sqp_builtin_dev(pmpc_context* ctx, int P, int
 template <class Model> pmpc_status linearise_impl(pmpc_context* ctx, int P, int S, double t0, double tf, const double* mp, int nmp, int B,
                                                   const double* var, const double* d, const double* lam, double* cost, double* constr, double* jac,
                                                   double* cost_grad, double* lag_grad, double* lag_hess);
+// the same launch on DEVICE buffers, every output given (cost: 2 per instance), asynchronous on the context's stream: what linearise_impl runs
+// between its staging copies, and the linearisation of pmpc_sqp_refine_batch_dev
+template <class Model> pmpc_status linearise_dev_impl(pmpc_context* ctx, int P, int S, double t0, double tf, const double* mp, int nmp, int B,
+                                                      const double* var, const double* d, const double* lam, double* cost, double* constr, double* jac,
+                                                      double* cost_grad, double* lag_grad, double* lag_hess);
 
 #ifdef PMPC_BUILTIN_DEFINITIONS
 #include <vector>
@@ -27,6 +32,22 @@ pmpc_status sqp_builtin_dev(pmpc_context* ctx, int P, int S, double t0, double t
                                    const pmpc_qp_settings* qs, double* x, double* lam, pmpc_sqp_info* info) {
     const Model mdl = make_model<Model>(mp, nmp);
     return pmpc::sqp_launch_dev<Model>(ctx, mdl, P, S, t0, tf, B, x_guess, lam_guess, d, lbx, ubx, lbg, ubg, ss, qs, x, lam, info);
+}
+
+template <class Model>
+pmpc_status linearise_dev_impl(pmpc_context* ctx, int P, int S, double t0, double tf, const double* mp, int nmp, int B,
+                               const double* var, const double* d, const double* lam, double* cost, double* constr, double* jac,
+                               double* cost_grad, double* lag_grad, double* lag_hess) {
+    const ChebData* cd = nullptr;
+    pmpc_status st = get_cheb(ctx, P, S, t0, tf, &cd);
+    if (st != PMPC_OK) return st;
+    const size_t lds = linearise_kernel_lds_bytes<Model>(P, S);
+    if (lds > ctx->lds_limit) return PMPC_ERR_UNSUPPORTED_SIZE;
+    HIPCHK(hipFuncSetAttribute((const void*)linearise_kernel<Model>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    Model mdl = make_model<Model>(mp, nmp);
+    hipLaunchKernelGGL(linearise_kernel<Model>, dim3(B), dim3(WAVE), lds, ctx->stream, mdl, cd, B, var, d, lam, cost, constr, jac, cost_grad, lag_grad, lag_hess);
+    HIPCHK(hipGetLastError());
+    return PMPC_OK;
 }
 
 template <class Model>
@@ -47,10 +68,8 @@ pmpc_status linearise_impl(pmpc_context* ctx, int P, int S, double t0, double tf
     double *dcg = stg.out<double>(SLOT_LIN_COST_GRAD, Bz * n), *dlg = stg.out<double>(SLOT_LIN_LAG_GRAD, Bz * n), *dlh = stg.out<double>(SLOT_LIN_LAG_HESS, Bz * n * n);
     if (!Model::ND) dd = stg.absent<double>();
     if (!stg.ok()) return stg.status;
-    HIPCHK(hipFuncSetAttribute((const void*)linearise_kernel<Model>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    Model mdl = make_model<Model>(mp, nmp);
-    hipLaunchKernelGGL(linearise_kernel<Model>, dim3(B), dim3(WAVE), lds, ctx->stream, mdl, cd, B, dvar, dd, dlam, dcost, dc, dj, dcg, dlg, dlh);
-    HIPCHK(hipGetLastError());
+    st = linearise_dev_impl<Model>(ctx, P, S, t0, tf, mp, nmp, B, dvar, dd, dlam, dcost, dc, dj, dcg, dlg, dlh);
+    if (st != PMPC_OK) return st;
     std::vector<double> c2(Bz * 2);
     stg.fetch(c2.data(), dcost, Bz * 2);
     if (constr) stg.fetch(constr, dc, Bz * m);
@@ -67,5 +86,7 @@ pmpc_status linearise_impl(pmpc_context* ctx, int P, int S, double t0, double tf
                                                 const double*, const double*, const double*, const double*, const double*, const double*, \
                                                 const pmpc_sqp_settings*, const pmpc_qp_settings*, double*, double*, pmpc_sqp_info*);    \
     template pmpc_status linearise_impl<Model>(pmpc_context*, int, int, double, double, const double*, int, int, const double*,         \
-                                               const double*, const double*, double*, double*, double*, double*, double*, double*);
+                                               const double*, const double*, double*, double*, double*, double*, double*, double*);        \
+    template pmpc_status linearise_dev_impl<Model>(pmpc_context*, int, int, double, double, const double*, int, int, const double*,     \
+                                                   const double*, const double*, double*, double*, double*, double*, double*, double*);
 #endif
