@@ -346,7 +346,7 @@ public:
         if (st == PMPC_OK) { m_x.swap(xo); m_lam.swap(lo); }
         return last_error() = st;
     }
-    // Newton steps on the active set of the solutions solve() left (pmpc_sqp_refine_batch; built-in OCPs on one device): primal_solution(b) /
+    // Newton steps on the active set of the solutions solve() left (pmpc_sqp_refine_batch, for a registered OCP pmpc_sqp_refine_batch_user; one device): primal_solution(b) /
     // dual_solution(b) go to the KKT point of their active set, an instance whose KKT residual does not improve keeps its solution
     // (PMPC_REFINE_REJECTED in refine_info(b).flags). act_tol: how close to a bound counts as active, the solver's eps_prim by default.
     // sens_idx / dz: variables pinned by an equality bound and the derivative of the solution with respect to their value (B * nsens * VAR_SIZE).
@@ -354,14 +354,13 @@ public:
         if (!m_multi.empty() || (!sens_idx.empty() && !dz)) return last_error() = PMPC_ERR_INVALID_ARGUMENT;
         pmpc_context* ctx = context();
         if (!ctx) return last_error();
-        const std::vector<double> mp = problem.model_params();
         m_refine_info.resize(B);
         if (dz) dz->assign((size_t)B * sens_idx.size() * VAR_SIZE, 0.0);
-        return last_error() = pmpc_sqp_refine_batch(ctx, device_binding<OCP>::model_id, OCP::POLY_ORDER, OCP::NUM_SEGMENTS, problem.t_start, problem.t_stop,
-                                                    mp.empty() ? nullptr : mp.data(), (int)mp.size(), B, m_p.data(), m_lbx.data(), m_ubx.data(),
-                                                    (NUM_INEQ > 0) ? m_lbg.data() : nullptr, (NUM_INEQ > 0) ? m_ubg.data() : nullptr, steps,
-                                                    act_tol < 0.0 ? m_settings.eps_prim : act_tol, m_x.data(), m_lam.data(), m_refine_info.data(),
-                                                    (int)sens_idx.size(), sens_idx.empty() ? nullptr : sens_idx.data(), dz ? dz->data() : nullptr);
+        return last_error() = device_binding<OCP>::refine(ctx, problem, OCP::POLY_ORDER, OCP::NUM_SEGMENTS, problem.t_start, problem.t_stop, B, m_p.data(),
+                                                          m_lbx.data(), m_ubx.data(), (NUM_INEQ > 0) ? m_lbg.data() : nullptr,
+                                                          (NUM_INEQ > 0) ? m_ubg.data() : nullptr, steps, act_tol < 0.0 ? m_settings.eps_prim : act_tol,
+                                                          m_x.data(), m_lam.data(), m_refine_info.data(), (int)sens_idx.size(),
+                                                          sens_idx.empty() ? nullptr : sens_idx.data(), dz ? dz->data() : nullptr);
     }
     const pmpc_refine_info& refine_info(int b) const noexcept { return m_refine_info[b]; }
     // the same solve with the batch in contiguous shards [k B / N, (k+1) B / N) over the N contexts of set_devices(), one host thread per shard
@@ -814,8 +813,8 @@ public:
         return last_error() = pmpc_mpc_batch_update(m_batch, nd > 0 ? m_p.data() : nullptr, m_lbx.data(), m_ubx.data(), num_ineq > 0 ? m_lbg.data() : nullptr,
                                                     num_ineq > 0 ? m_ubg.data() : nullptr);
     }
-    // Newton steps on the active set of every controller's iterate, in place on the device (pmpc_mpc_batch_refine; a built-in OCP only — a
-    // registered one is refused with PMPC_ERR_UNKNOWN_MODEL): the SQP-tolerance answer of step() taken to the KKT point of its active set, an
+    // Newton steps on the active set of every controller's iterate, in place on the device (pmpc_mpc_batch_refine; a registered OCP after
+    // enable_refine() — without it the call is refused with PMPC_ERR_UNKNOWN_MODEL): the SQP-tolerance answer of step() taken to the KKT point of its active set, an
     // instance that does not improve keeps its iterate (PMPC_REFINE_REJECTED in refine_info(b).flags). gain receives B * nu * nx values,
     // gain[(b * nu + c) * nx + j] = d u_c(t_start) / d x0_j: the first-order feedback of controller b around its solution. act_tol: how close
     // to a bound counts as active — the solver's eps_prim by default.
@@ -823,6 +822,15 @@ public:
         if (!m_batch) return PMPC_ERR_INVALID_ARGUMENT;
         gain.resize((size_t)B * nu * nx); m_refine_info.resize(B);
         return last_error() = pmpc_mpc_batch_refine(m_batch, steps, act_tol < 0.0 ? m_settings.eps_prim : act_tol, gain.data(), m_refine_info.data());
+    }
+    // A registered OCP's batch is given its lineariser (pmpc_mpc_batch_set_lineariser), after which refine() serves it; nothing does this implicitly.
+    // Callable before the first step(). PMPC_ERR_INVALID_ARGUMENT for a built-in OCP (it needs none), or when the device library lacks
+    // pmpc_user_lin_dev_<DeviceModel> (built before the symbol existed).
+    pmpc_status enable_refine() noexcept {
+        if (!device_binding<OCP>::lin_fn()) return last_error() = PMPC_ERR_INVALID_ARGUMENT;
+        if (m_batch) { const pmpc_status st = pmpc_mpc_batch_set_lineariser(m_batch, device_binding<OCP>::lin_fn()); if (st != PMPC_OK) return last_error() = st; }
+        m_refine_enabled = true;
+        return last_error() = PMPC_OK;
     }
     const pmpc_refine_info& refine_info(int b) const noexcept { return m_refine_info[b]; }
     const pmpc_sqp_info& info(int b) const noexcept { return m_info[b]; }
@@ -865,6 +873,7 @@ private:
                 const pmpc_status ps = pmpc_mpc_batch_set_plant(m_batch, &m_plant, m_plant_d.empty() ? nullptr : m_plant_d.data(), device_binding<OCP>::plant_fn());
                 if (ps != PMPC_OK) return ps;
             }
+            if (m_refine_enabled) { const pmpc_status ls = pmpc_mpc_batch_set_lineariser(m_batch, device_binding<OCP>::lin_fn()); if (ls != PMPC_OK) return ls; }
         }
         pmpc_sqp_settings_default(&ss);
         ss.tau = m_settings.tau; ss.eta = m_settings.eta; ss.rho = m_settings.rho; ss.eps_prim = m_settings.eps_prim; ss.eps_dual = m_settings.eps_dual;
@@ -880,7 +889,7 @@ private:
     sqp_settings_t m_settings; qp_solver_settings_t m_qp_settings;
     pmpc_mpc_batch* m_batch{nullptr};
     int m_dispatch_mode{0}, m_iter_weight{default_iter_weight};
-    pmpc_plant_settings m_plant{1, 1, 0}; bool m_has_plant{false};
+    pmpc_plant_settings m_plant{1, 1, 0}; bool m_has_plant{false}, m_refine_enabled{false};
 public:
     LSFilterHandle filter;   // the solvers' LSFilter members (used when settings().line_search == 1)
 };
@@ -892,6 +901,14 @@ template <class OCP, int MODEL_ID> struct builtin_device_binding {
     static constexpr int model_id = MODEL_ID;   // what BatchSolver's prioritised solve asks for
     static constexpr bool registered = false;
     static pmpc_plant_dev_fn plant_fn() { return nullptr; }
+    static pmpc_lin_dev_fn lin_fn() { return nullptr; }
+    static pmpc_status refine(pmpc_context* ctx, const OCP& ocp, int P, int S, double t0, double tf, int B, const double* d, const double* lbx,
+                              const double* ubx, const double* lbg, const double* ubg, int steps, double act_tol, double* x, double* lam,
+                              pmpc_refine_info* info, int nsens, const int* sens_idx, double* dz) {
+        const std::vector<double> mp = ocp.model_params();
+        return pmpc_sqp_refine_batch(ctx, MODEL_ID, P, S, t0, tf, mp.empty() ? nullptr : mp.data(), (int)mp.size(), B, d, lbx, ubx, lbg, ubg, steps, act_tol,
+                                     x, lam, info, nsens, sens_idx, dz);
+    }
     static pmpc_status plant_step(pmpc_context* ctx, const OCP& ocp, int P, int S, double t0, double tf, int B, double dt, const pmpc_plant_settings* ps,
                                   double* state, const double* u0, const double* iterate, const double* d, const double* w) {
         const std::vector<double> mp = ocp.model_params();
@@ -924,9 +941,22 @@ template <class OCP, int MODEL_ID> struct builtin_device_binding {
     extern "C" pmpc_status pmpc_user_plant_dev_##DeviceModel(pmpc_context*, const void*, int, int, double, double, int, double,       \
                                                              const pmpc_plant_settings*, double*, const double*, const double*,       \
                                                              const double*, const double*) __attribute__((weak));                     \
+    /* weak, as the plant: lin_fn() is null for a device library built before the lineariser symbol existed */                        \
+    extern "C" pmpc_status pmpc_user_lin_dev_##DeviceModel(pmpc_context*, const void*, int, int, double, double, int, const double*,  \
+                                                           const double*, const double*, double*, double*, double*, double*, double*, \
+                                                           double*) __attribute__((weak));                                            \
     template <> struct polympc::device_binding<Name> {                                                                                \
         static constexpr bool registered = true;                                                                                      \
         static pmpc_plant_dev_fn plant_fn() { return &pmpc_user_plant_dev_##DeviceModel; }                                            \
+        static pmpc_lin_dev_fn lin_fn() { return &pmpc_user_lin_dev_##DeviceModel; }                                                  \
+        static pmpc_status refine(pmpc_context* ctx, const Name& ocp, int P, int S, double t0, double tf, int B, const double* d,     \
+                                  const double* lbx, const double* ubx, const double* lbg, const double* ubg, int steps,              \
+                                  double act_tol, double* x, double* lam, pmpc_refine_info* info, int nsens, const int* sens_idx,     \
+                                  double* dz) {                                                                                       \
+            const auto dm = ocp.device_model();                                                                                       \
+            return pmpc_sqp_refine_batch_user(ctx, lin_fn(), &dm, Name::NX, Name::NU, Name::NP, Name::ND, Name::NG, P, S, t0, tf, B,  \
+                                              d, lbx, ubx, lbg, ubg, steps, act_tol, x, lam, info, nsens, sens_idx, dz);              \
+        }                                                                                                                             \
         static pmpc_status plant_step(pmpc_context* ctx, const Name& ocp, int P, int S, double t0, double tf, int B, double dt,       \
                                       const pmpc_plant_settings* ps, double* state, const double* u0, const double* iterate,          \
                                       const double* d, const double* w) {                                                             \

@@ -15,6 +15,8 @@
 //                       -I<repo>/include -L<repo>/polympc_amd -lpolympc_amd -o libmy_ocp.so
 // This emits the C symbols pmpc_user_sqp_dev_MyOCP (device buffers, type pmpc_sqp_dev_fn), pmpc_user_dims_MyOCP and pmpc_user_plant_dev_MyOCP
 // (type pmpc_plant_dev_fn: one control period of x' = dynamics_impl integrated on the device, the plant of a closed loop — pmpc_plant.hpp).
+// and pmpc_user_lin_dev_MyOCP (type pmpc_lin_dev_fn: the collocation assembly with the exact Lagrangian Hessian at given points, the linearisation of
+// pmpc_ocp_linearise_batch_user and of the KKT refinement pmpc_sqp_refine_batch_user / pmpc_mpc_batch_set_lineariser).
 // Host code (any C++ compiler) then uses polympc::Solver<...> from <polympc/polympc.hpp> with POLYMPC_USE_REGISTERED_OCP.
 #pragma once
 #include "../polympc_amd.h"
@@ -40,4 +42,12 @@
         if (!model) return PMPC_ERR_INVALID_ARGUMENT;                                                                            \
         return pmpc::plant_launch_dev<Name>(ctx, *static_cast<const Name*>(model), P, S, t0, tf, B, dt, settings, state, u0,     \
                                             iterate, d, w);                                                                      \
+    }                                                                                                                            \
+    extern "C" pmpc_status pmpc_user_lin_dev_##Name(pmpc_context* ctx, const void* model, int P, int S, double t0, double tf,    \
+                                                    int B, const double* var, const double* d, const double* lam, double* cost, \
+                                                    double* constr, double* jac, double* cost_grad, double* lag_grad,           \
+                                                    double* lag_hess) {                                                         \
+        if (!model) return PMPC_ERR_INVALID_ARGUMENT;                                                                            \
+        return pmpc::linearise_launch_dev<Name>(ctx, *static_cast<const Name*>(model), P, S, t0, tf, B, var, d, lam, cost,       \
+                                                constr, jac, cost_grad, lag_grad, lag_hess);                                     \
     }

@@ -298,6 +298,13 @@ pmpc_status pmpc_ocp_linearise_batch(pmpc_context* ctx, int model, int P, int S,
                                      const double* mparams, int n_mparams, int B, const double* var, const double* d,
                                      const double* lam, double* cost, double* constr, double* jac, double* cost_grad,
                                      double* lag_grad, double* lag_hess);
+/* The same launch on device pointers, asynchronous on the context's stream: every output is given; cost holds 2 values per instance, as the host form
+ * writes it — the cost of the assembly and the cost of the values-only path of the line search. lam NULL = zeros.
+ * PMPC_ERR_INVALID_ARGUMENT before any device call for a NULL ctx, var or output, B < 0, d NULL with ND > 0. B == 0: nothing is done. */
+pmpc_status pmpc_ocp_linearise_batch_dev(pmpc_context* ctx, int model, int P, int S, double t0, double tf,
+                                         const double* mparams, int n_mparams, int B, const double* var, const double* d,
+                                         const double* lam, double* cost, double* constr, double* jac, double* cost_grad,
+                                         double* lag_grad, double* lag_hess);
 
 /* Batched SQPBase::solve (replaces Solver<OCP>::solve() = SQPBase::solve, sqp_base.hpp:569-696, with
  * linearisation :310-318, update_linearisation :490-504 + BFGS_update bfgs.hpp:23-52, step_size_selection
@@ -487,7 +494,8 @@ pmpc_status pmpc_sqp_solve_batch_user(pmpc_context* ctx, pmpc_sqp_dev_fn fn, con
  * the batch is gathered into dispatch order, solved and scattered back, and priority receives iter_weight * iter + qp_solver_iter of this step;
  * a non-NULL filter_state / iteration_trace is then refused. PMPC_ERR_INVALID_ARGUMENT before any device call for a NULL ctx, fn, model, x0,
  * lbx, ubx, settings, x, lam or info; nx < 1; nu, np, nd, ng or B < 0; P or S < 1; nd > 0 without d; ng > 0 without lbg / ubg; max_iter < 1; a
- * regularisation or kkt_form outside 0 .. 2. A status returned by fn is passed through. Linearisation, the one-off prioritised solve and the sharded solve have no registered form. */
+ * regularisation or kkt_form outside 0 .. 2. A status returned by fn is passed through. The one-off prioritised solve and the sharded solve have no registered form; linearisation and
+ * refinement have one (pmpc_ocp_linearise_batch_user, pmpc_sqp_refine_batch_user, pmpc_mpc_batch_set_lineariser, below). */
 pmpc_status pmpc_mpc_step_batch_user_dev(pmpc_context* ctx, pmpc_sqp_dev_fn fn, const void* model, int nx, int nu, int np, int nd, int ng,
                                          int P, int S, double t0, double tf, int B, const double* x0, const double* d, double* lbx, double* ubx,
                                          const double* lbg, const double* ubg, const pmpc_sqp_settings* sqp_settings,
@@ -720,8 +728,45 @@ pmpc_status pmpc_sqp_refine_batch(pmpc_context* ctx, int model, int P, int S, do
 /* On an opaque batch of a built-in OCP: refines the batch's iterate in place with its own bounds and static parameters; sens_idx = the last nx
  * entries of the x block (the pinned measured state). gain (host, B * nu * nx, may be NULL): gain[(b * nu + c) * nx + j] = d u_c(t_start) / d x0_j,
  * the rows of dz at the last node of the u block — the first-order feedback of the controller around its solution; zeros for a rejected instance.
- * info (host, B, may be NULL). A registered OCP's batch has no linearisation entry: PMPC_ERR_UNKNOWN_MODEL. The call synchronises. */
+ * info (host, B, may be NULL). A registered OCP's batch is served once it has been given its lineariser (pmpc_mpc_batch_set_lineariser, below);
+ * as created it has no linearisation entry: PMPC_ERR_UNKNOWN_MODEL. The call synchronises. */
 pmpc_status pmpc_mpc_batch_refine(pmpc_mpc_batch* batch, int steps, double act_tol, double* gain, pmpc_refine_info* info);
+
+/* ---- registered OCPs: linearisation, refinement and feedback gains ---------------------------------------------------------------------
+ * The lineariser of a registered OCP: the symbol pmpc_user_lin_dev_<Name> that PMPC_REGISTER_OCP emits — the kernel of pmpc_ocp_linearise_batch
+ * compiled for the user's model. Device pointers, every output given, asynchronous on the context's stream; cost is 2 per instance, as
+ * pmpc_ocp_linearise_batch writes it; lam NULL = zeros; model NULL: PMPC_ERR_INVALID_ARGUMENT. */
+typedef pmpc_status (*pmpc_lin_dev_fn)(pmpc_context* ctx, const void* model, int P, int S, double t0, double tf, int B, const double* var,
+                                       const double* d, const double* lam, double* cost, double* constr, double* jac, double* cost_grad,
+                                       double* lag_grad, double* lag_hess);
+/* pmpc_ocp_linearise_batch[_dev] of a registered OCP: lin_fn and model in place of the model id, the OCP's dimensions as numbers as for
+ * pmpc_mpc_step_batch_user_dev (nn = P * S + 1, n = (nx + nu) * nn + np, m = (nx + ng) * nn). The _dev form takes device pointers with every
+ * output given and is asynchronous on the context's stream; the host form accepts NULL for any output, copies in, linearises, copies out and
+ * synchronises. Refused before any device call, outputs untouched — PMPC_ERR_INVALID_ARGUMENT: a NULL ctx, lin_fn, model or var (_dev: or output);
+ * nx < 1; nu, np, nd, ng or B < 0; P or S < 1; nd > 0 without d. PMPC_ERR_UNSUPPORTED_SIZE: a grid beyond P <= 15, P * S + 1 <= 64, or one whose
+ * linearisation does not fit the LDS of a workgroup (answered by lin_fn). B == 0: nothing is done. A status returned by lin_fn is passed through. */
+pmpc_status pmpc_ocp_linearise_batch_user_dev(pmpc_context* ctx, pmpc_lin_dev_fn lin_fn, const void* model, int nx, int nu, int np, int nd, int ng,
+                                              int P, int S, double t0, double tf, int B, const double* var, const double* d, const double* lam,
+                                              double* cost, double* constr, double* jac, double* cost_grad, double* lag_grad, double* lag_hess);
+pmpc_status pmpc_ocp_linearise_batch_user(pmpc_context* ctx, pmpc_lin_dev_fn lin_fn, const void* model, int nx, int nu, int np, int nd, int ng,
+                                          int P, int S, double t0, double tf, int B, const double* var, const double* d, const double* lam,
+                                          double* cost, double* constr, double* jac, double* cost_grad, double* lag_grad, double* lag_hess);
+/* pmpc_sqp_refine_batch[_dev] of a registered OCP: steps 1 - 7 above with lin_fn as the linearisation of step 1; lin_fn, model and the five
+ * dimensions stand in place of model, mparams and n_mparams. Refusals as for the built-in form, with those of the linearisation above in place
+ * of PMPC_ERR_UNKNOWN_MODEL, and lbg / ubg NULL with ng > 0. */
+pmpc_status pmpc_sqp_refine_batch_user_dev(pmpc_context* ctx, pmpc_lin_dev_fn lin_fn, const void* model, int nx, int nu, int np, int nd, int ng,
+                                           int P, int S, double t0, double tf, int B, const double* d, const double* lbx, const double* ubx,
+                                           const double* lbg, const double* ubg, int steps, double act_tol, double* x, double* lam,
+                                           pmpc_refine_info* info, int nsens, const int* sens_idx, double* dz);
+pmpc_status pmpc_sqp_refine_batch_user(pmpc_context* ctx, pmpc_lin_dev_fn lin_fn, const void* model, int nx, int nu, int np, int nd, int ng,
+                                       int P, int S, double t0, double tf, int B, const double* d, const double* lbx, const double* ubx,
+                                       const double* lbg, const double* ubg, int steps, double act_tol, double* x, double* lam,
+                                       pmpc_refine_info* info, int nsens, const int* sens_idx, double* dz);
+/* The lineariser of an opaque batch of a registered OCP: the batch keeps lin_fn (it holds its own copy of the model object already), and
+ * pmpc_mpc_batch_refine then serves the handle exactly as it serves a built-in one. Nothing installs it implicitly: without this call the refine
+ * of a registered batch keeps answering PMPC_ERR_UNKNOWN_MODEL. PMPC_ERR_INVALID_ARGUMENT before any device call: a NULL batch, a NULL lin_fn on a
+ * registered batch, a non-NULL one on a built-in batch (the rule of pmpc_mpc_batch_set_plant). */
+pmpc_status pmpc_mpc_batch_set_lineariser(pmpc_mpc_batch* batch, pmpc_lin_dev_fn lin_fn);
 
 #ifdef __cplusplus
 }

@@ -112,6 +112,8 @@ _TRAJ_REGRID = _I, _TRAJ_HEAD + [_I] * 4 + [_D, _D, _P, _P]               # P, S
 _PLANT = _I, [_V, _I, _P, _I, _I, _I, _D, _D] + _PLANT_TAIL               # ctx, model, mparams, n_mparams, P, S, t0, tf, ...
 _POLISH = _I, _QP_HEAD + [_P] * 9 + [_D, _I, _V, _I, _V, _P, _P, _V, _P]     # H .. xub, p_in, y_in, act_tol, frozen, masks, nsens, sens_idx, p, y, info, dP
 _REFINE = _I, [_V] + _OCP_GRID + [_I] + [_P] * 5 + [_I, _D, _P, _P, _V, _I, _V, _P]   # ..., B, d, lbx, ubx, lbg, ubg, steps, act_tol, x, lam, info, nsens, sens_idx, dz
+_LIN_USER = _I, _USER_OCP_HEAD + _USER_OCP_GRID + [_I] + [_P] * 9         # ctx, lin_fn, model, nx .. tf, B, var, d, lam, cost, constr, jac, cost_grad, lag_grad, lag_hess
+_REFINE_USER = _I, _USER_OCP_HEAD + _USER_OCP_GRID + _REFINE[1][8:]        # ctx, lin_fn, model, nx .. tf, B, d, ... as _REFINE
 _PLANT_USER = _I, _USER_OCP_HEAD + [_I] * 6 + [_D, _D] + _PLANT_TAIL      # ctx, fn, model, nx, nu, np, nd, P, S, t0, tf, ...
 
 SIGNATURES = {
@@ -146,6 +148,7 @@ SIGNATURES = {
     # ---- built-in OCPs: dimensions, linearisation, SQP solves, filter and trace handles
     "pmpc_ocp_dims": (_I, [_I, _I, _I] + [_V] * 8),
     "pmpc_ocp_linearise_batch": (_I, [_V] + _OCP_GRID + [_I] + [_P] * 9),
+    "pmpc_ocp_linearise_batch_dev": (_I, [_V] + _OCP_GRID + [_I] + [_P] * 9),
     "pmpc_sqp_solve_batch": _SQP,
     "pmpc_sqp_solve_batch_multi": (_I, [_H, _I] + _OCP_GRID + [_I] + _SQP_IN + _SQP_TAIL),
     "pmpc_sqp_solve_batch_dev": _SQP,
@@ -204,6 +207,12 @@ SIGNATURES = {
     "pmpc_sqp_refine_batch_dev": _REFINE,
     "pmpc_sqp_refine_batch": _REFINE,
     "pmpc_mpc_batch_refine": (_I, [_V, _I, _D, _P, _V]),
+    # ---- registered OCPs: linearisation, refinement, the lineariser of a batch
+    "pmpc_ocp_linearise_batch_user_dev": _LIN_USER,
+    "pmpc_ocp_linearise_batch_user": _LIN_USER,
+    "pmpc_sqp_refine_batch_user_dev": _REFINE_USER,
+    "pmpc_sqp_refine_batch_user": _REFINE_USER,
+    "pmpc_mpc_batch_set_lineariser": (_I, [_V, _V]),
 }
 EXPORTED_SYMBOLS = list(SIGNATURES)
 
@@ -377,7 +386,7 @@ class UserOCP:
         lib()   # loaded first: the user's library finds the product library it was linked against by its soname, wherever it lies
         self.so = C.CDLL(os.path.abspath(so_path))
         self.fn = getattr(self.so, "pmpc_user_sqp_dev_" + name)
-        self.name, self._plant_fn = name, None
+        self.name, self._plant_fn, self._lin_fn = name, None, None
         v = [C.c_int() for _ in range(5)]
         getattr(self.so, "pmpc_user_dims_" + name)(*[C.byref(a) for a in v])
         self.nx, self.nu, self.np, self.nd, self.ng = [a.value for a in v]
@@ -443,8 +452,63 @@ class UserOCP:
         """pmpc_plant_step_batch_user_dev on torch CUDA tensors: state (B, nx) advanced in place; asynchronous on the context's stream"""
         self._plant_call(lib().pmpc_plant_step_batch_user_dev, ctx, P, S, t0, tf, B, dt, settings, [_d(a) for a in (state, u0, iterate, d, w)])
 
+    @property
+    def lin_fn(self):
+        """pmpc_user_lin_dev_<name>, looked up when a linearisation is first used: a user library built before the symbol existed keeps loading"""
+        if self._lin_fn is None:
+            try:
+                self._lin_fn = getattr(self.so, "pmpc_user_lin_dev_" + self.name)
+            except AttributeError:
+                raise RuntimeError(f"the library of the registered OCP {self.name} has no pmpc_user_lin_dev_{self.name}: rebuild it "
+                                   "against this include/polympc/register_ocp.hpp") from None
+        return self._lin_fn
+
+    def _lin_head(self, ctx):
+        return ctx._ctx, C.cast(self.lin_fn, C.c_void_p), C.cast(self.model, C.c_void_p)
+
+    def linearise_batch(self, ctx, P, S, t0, tf, var, d, lam=None):
+        """pmpc_ocp_linearise_batch_user (host buffers) -> the dict of Context.ocp_linearise_batch"""
+        dm = self.dims(P, S); n, m = dm["n"], dm["m"]
+        vk, vp = _h(np.atleast_2d(var)); B = vk.shape[0]
+        dk, dp_ = _h(d); lk, lp = _h(lam)
+        cost = np.zeros((B, 2)); c = np.zeros((B, m)); jac = np.zeros((B, m * n)); cg = np.zeros((B, n)); lg = np.zeros((B, n))
+        lh = np.zeros((B, n * n))
+        P_ = C.POINTER(C.c_double)
+        _check_status(lib().pmpc_ocp_linearise_batch_user(*self._lin_head(ctx), *self._grid(P, S, t0, tf), B, vp, dp_, lp,
+                                                          *[a.ctypes.data_as(P_) for a in (cost, c, jac, cg, lg, lh)]))
+        return dict(cost=cost[:, 0], cost_values_only=cost[:, 1], c=c, jac=jac.reshape(B, n, m).transpose(0, 2, 1).copy(),
+                    cost_grad=cg, lag_grad=lg, lag_hess=lh.reshape(B, n, n).transpose(0, 2, 1).copy())
+
+    def linearise_batch_dev(self, ctx, P, S, t0, tf, B, var, d, lam, cost, constr, jac, cost_grad, lag_grad, lag_hess):
+        """pmpc_ocp_linearise_batch_user_dev on torch CUDA tensors in the library's layout (cost (B, 2), jac (B, n, m) and lag_hess (B, n, n)
+        column-major per instance; lam None = zeros); asynchronous on the context's stream"""
+        _check_status(lib().pmpc_ocp_linearise_batch_user_dev(*self._lin_head(ctx), *self._grid(P, S, t0, tf), int(B),
+                                                              *[_d(a) for a in (var, d, lam, cost, constr, jac, cost_grad, lag_grad, lag_hess)]))
+
+    def sqp_refine(self, ctx, P, S, t0, tf, x, lam, d, lbx, ubx, lbg=None, ubg=None, steps=3, act_tol=1e-3, sens_idx=None):
+        """pmpc_sqp_refine_batch_user (host buffers): Context.sqp_refine for this OCP -> x, lam (new arrays), info (REFINE_INFO_DTYPE), dz (B, nsens, n)"""
+        x = np.array(np.atleast_2d(x), dtype=np.float64, order="C"); lam = np.array(np.atleast_2d(lam), dtype=np.float64, order="C")
+        B, n = x.shape
+        sens = np.ascontiguousarray([] if sens_idx is None else sens_idx, dtype=np.int32); ns = int(sens.size)
+        dz = np.zeros((B, ns, n)); info = np.zeros(B, dtype=REFINE_INFO_DTYPE)
+        keep = [_h(a) for a in (d, lbx, ubx, lbg, ubg)]
+        P_ = C.POINTER(C.c_double)
+        _check_status(lib().pmpc_sqp_refine_batch_user(*self._lin_head(ctx), *self._grid(P, S, t0, tf), B, *[k[1] for k in keep], int(steps), float(act_tol),
+                                                       x.ctypes.data_as(P_), lam.ctypes.data_as(P_), C.c_void_p(info.ctypes.data), ns,
+                                                       C.c_void_p(sens.ctypes.data) if ns else None, dz.ctypes.data_as(P_) if ns else None))
+        return x, lam, info, dz
+
+    def sqp_refine_dev(self, ctx, P, S, t0, tf, B, x, lam, info, d, lbx, ubx, lbg=None, ubg=None, steps=3, act_tol=1e-3, sens_idx=None, dz=None):
+        """pmpc_sqp_refine_batch_user_dev on torch CUDA tensors, x and lam in place (info: uint8 of B * 32 bytes; sens_idx: a host sequence of ints);
+        asynchronous on the context's stream"""
+        sens = np.ascontiguousarray([] if sens_idx is None else sens_idx, dtype=np.int32); ns = int(sens.size)
+        _check_status(lib().pmpc_sqp_refine_batch_user_dev(*self._lin_head(ctx), *self._grid(P, S, t0, tf), int(B), _d(d), _d(lbx), _d(ubx), _d(lbg), _d(ubg),
+                                                           int(steps), float(act_tol), _d(x), _d(lam), _dv(info), ns,
+                                                           C.c_void_p(sens.ctypes.data) if ns else None, _d(dz)))
+
     def mpc_batch(self, ctx, P, S, t0, tf, B, d, lbx, ubx, lbg=None, ubg=None, x_guess=None, lam_guess=None):
-        """pmpc_mpc_batch_create_user: B controllers of this OCP whose data stay on the device between steps (MPCBatch)"""
+        """pmpc_mpc_batch_create_user: B controllers of this OCP whose data stay on the device between steps (MPCBatch). The batch refines only
+        after MPCBatch.set_lineariser()."""
         return MPCBatch(ctx, self, P, S, t0, tf, B, d, lbx, ubx, lbg, ubg, x_guess, lam_guess)
 
 
@@ -537,12 +601,16 @@ class MPCBatch:
         _check_status(lib().pmpc_mpc_batch_shift(self._batch, float(dt), 1 if duals else 0))
 
     def refine(self, steps=3, act_tol=1e-3, want_gain=True):
-        """pmpc_mpc_batch_refine: Newton steps on the active set of the batch's iterate, in place (a built-in OCP's batch only)
+        """pmpc_mpc_batch_refine: Newton steps on the active set of the batch's iterate, in place (a registered OCP's batch: after set_lineariser())
         -> gain (B, nu, nx) = d u(t_start) / d x0 (None unless wanted; zeros for a rejected instance), info (REFINE_INFO_DTYPE)"""
         gain = np.zeros((self.B, self.dims["nu"], self.dims["nx"])) if want_gain else None
         info = np.zeros(self.B, dtype=REFINE_INFO_DTYPE)
         _check_status(lib().pmpc_mpc_batch_refine(self._batch, int(steps), float(act_tol), _h(gain)[1], C.c_void_p(info.ctypes.data)))
         return gain, info
+
+    def set_lineariser(self):
+        """pmpc_mpc_batch_set_lineariser: a registered OCP's batch is given its pmpc_user_lin_dev_<name>, after which refine() serves it"""
+        _check_status(lib().pmpc_mpc_batch_set_lineariser(self._batch, C.cast(self._user.lin_fn, C.c_void_p) if self._user is not None else None))
 
     def set_plant(self, settings=None, d_plant=None):
         """pmpc_mpc_batch_set_plant: the plant of rollout() — settings (default: RK4, 1 substep, zero-order hold) and the plant's own static
@@ -724,6 +792,13 @@ class Context:
                                                       C.c_void_p(sens.ctypes.data) if ns else None, _d(dz)))
 
     # ------------------------------------------------------------------ collocation assembly (host buffers)
+    def ocp_linearise_batch_dev(self, model, P, S, t0, tf, B, var, d, lam, cost, constr, jac, cost_grad, lag_grad, lag_hess, mparams=None):
+        """pmpc_ocp_linearise_batch_dev on torch CUDA tensors in the library's layout (cost (B, 2), jac (B, n, m) and lag_hess (B, n, n) column-major
+        per instance; lam None = zeros); asynchronous on the context's stream"""
+        mk, mp = _h(mparams)
+        _check_status(lib().pmpc_ocp_linearise_batch_dev(self._ctx, int(model), int(P), int(S), float(t0), float(tf), mp, 0 if mk is None else len(mk), int(B),
+                                                         *[_d(a) for a in (var, d, lam, cost, constr, jac, cost_grad, lag_grad, lag_hess)]))
+
     def ocp_linearise_batch(self, model, P, S, t0, tf, var, d, lam=None, mparams=None):
         dm = ocp_dims(model, P, S); n, m = dm["n"], dm["m"]
         vk, vp = _h(var); B = vk.shape[0]

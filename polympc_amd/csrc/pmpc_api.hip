@@ -26,8 +26,8 @@ extern "C" pmpc_status pmpc_internal_services(pmpc_context* ctx, int P, int S, d
     const ChebData* cd = nullptr;
     pmpc_status st = get_cheb(ctx, P, S, t0, tf, &cd);
     if (st != PMPC_OK) return st;
-    st = ensure_ws(ctx, ws_bytes);
-    if (st != PMPC_OK) return st;
+    // (a launch that asks for no workspace leaves it alone, also under the poison harness: the refinement keeps its state there between linearisations)
+    if (ws_bytes) { st = ensure_ws(ctx, ws_bytes); if (st != PMPC_OK) return st; }
     PMPC_POISON_DEVICE(ctx);   // (developer harness: every fused SQP launch asks for its services first)
     *cheb = cd; *ws = ctx->ws; *stream = (void*)ctx->stream; *lds_limit = ctx->lds_limit; *phase_cycles = ctx->phase_cycles;
     *force_lds = ctx->force_lds_path ? 1 : 0;
@@ -272,6 +272,17 @@ pmpc_status pmpc_ocp_linearise_batch(pmpc_context* ctx, int model, int P, int S,
     DISPATCH_MODEL(model, linearise_impl, ctx, P, S, t0, tf, mparams, n_mparams, B, var, d, lam, cost, constr, jac, cost_grad, lag_grad, lag_hess);
 }
 
+pmpc_status pmpc_ocp_linearise_batch_dev(pmpc_context* ctx, int model, int P, int S, double t0, double tf, const double* mparams,
+                                         int n_mparams, int B, const double* var, const double* d, const double* lam, double* cost,
+                                         double* constr, double* jac, double* cost_grad, double* lag_grad, double* lag_hess) {
+    if (!ctx || B < 0 || !var || !cost || !constr || !jac || !cost_grad || !lag_grad || !lag_hess) return PMPC_ERR_INVALID_ARGUMENT;
+    { int nd = 0; const pmpc_status ds = pmpc_ocp_dims(model, P, S, nullptr, nullptr, nullptr, &nd, nullptr, nullptr, nullptr, nullptr);
+      if (ds != PMPC_OK) return ds;
+      if (nd > 0 && !d) return PMPC_ERR_INVALID_ARGUMENT; }
+    if (B == 0) return PMPC_OK;
+    DISPATCH_MODEL(model, linearise_dev_impl, ctx, P, S, t0, tf, mparams, n_mparams, B, var, d, lam, cost, constr, jac, cost_grad, lag_grad, lag_hess);
+}
+
 /* The argument check of pmpc_sqp_solve_batch and its _dev twin, run before the first device call; callers return PMPC_OK for B == 0. The static
  * parameters `d` are mandatory for models that have them (ND > 0), and at least one SQP iteration must be allowed (max_iter <= 0 would launch
  * nothing and leave the outputs unwritten). The host wrapper has always answered an empty batch first, and regularisation after the model, the
@@ -400,6 +411,7 @@ struct pmpc_mpc_batch {
     pmpc_sqp_info* info = nullptr;
     int dispatch_mode = 0, iter_weight = 0; int* priority = nullptr; bool stepped = false;   // pmpc_mpc_batch_set_dispatch
     bool has_plant = false; pmpc_plant_settings plant{}; pmpc_plant_dev_fn plant_fn = nullptr; double* d_plant = nullptr;   // pmpc_mpc_batch_set_plant
+    pmpc_lin_dev_fn lin_fn = nullptr;   // pmpc_mpc_batch_set_lineariser: a registered OCP's linearisation, for pmpc_mpc_batch_refine
     void* roll[5] = {nullptr}; size_t roll_bytes[5] = {0};   // pmpc_mpc_batch_rollout: xs, us, info, w and the w of one step; they only grow
 };
 pmpc_status pmpc_mpc_batch_destroy(pmpc_mpc_batch* h) {
@@ -505,7 +517,7 @@ pmpc_status pmpc_mpc_batch_solution(pmpc_mpc_batch* h, double* x, double* lam) {
 }
 pmpc_status pmpc_mpc_batch_refine(pmpc_mpc_batch* h, int steps, double act_tol, double* gain, pmpc_refine_info* info) {
     if (!h || steps < 0 || steps > PMPC_REFINE_MAX_STEPS || !(act_tol >= 0.0)) return PMPC_ERR_INVALID_ARGUMENT;
-    if (h->solve.fn) return PMPC_ERR_UNKNOWN_MODEL;   // a registered OCP has no linearisation entry
+    if (h->solve.fn && !h->lin_fn) return PMPC_ERR_UNKNOWN_MODEL;   // a registered OCP's batch that was not given its lineariser has no linearisation entry
     pmpc_context* ctx = h->ctx;
     const DevSolver& sv = h->solve;
     const OcpSizes& z = h->z;
@@ -519,8 +531,10 @@ pmpc_status pmpc_mpc_batch_refine(pmpc_mpc_batch* h, int steps, double act_tol, 
     pmpc_status st = ensure_scratch(ctx, SLOT_QP_X, (size_t)B * nx * n * sizeof(double), &dzv);
     if (st == PMPC_OK) st = ensure_scratch(ctx, SLOT_QP_INFO, (size_t)B * sizeof(pmpc_refine_info), &infov);
     if (st != PMPC_OK) return st;
-    st = pmpc_sqp_refine_batch_dev(ctx, sv.model, sv.P, sv.S, sv.t0, sv.tf, sv.mparams, sv.n_mparams, B, h->d, h->lbx, h->ubx, h->lbg, h->ubg, steps, act_tol,
-                                   h->x, h->lam, (pmpc_refine_info*)infov, nx, sens, (double*)dzv);
+    st = sv.fn ? pmpc_sqp_refine_batch_user_dev(ctx, h->lin_fn, sv.user, z.nx, z.nu, z.np, z.nd, z.ng, sv.P, sv.S, sv.t0, sv.tf, B, h->d, h->lbx, h->ubx, h->lbg,
+                                                h->ubg, steps, act_tol, h->x, h->lam, (pmpc_refine_info*)infov, nx, sens, (double*)dzv)
+               : pmpc_sqp_refine_batch_dev(ctx, sv.model, sv.P, sv.S, sv.t0, sv.tf, sv.mparams, sv.n_mparams, B, h->d, h->lbx, h->ubx, h->lbg, h->ubg, steps, act_tol,
+                                           h->x, h->lam, (pmpc_refine_info*)infov, nx, sens, (double*)dzv);
     if (st != PMPC_OK) return st;
     std::vector<double> dz(gain ? (size_t)B * nx * n : 0);
     if (gain) HIPCHK(hipMemcpyAsync(dz.data(), dzv, dz.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
@@ -530,6 +544,11 @@ pmpc_status pmpc_mpc_batch_refine(pmpc_mpc_batch* h, int steps, double act_tol, 
         for (int b = 0; b < B; ++b)
             for (int c = 0; c < nu; ++c)
                 for (int j = 0; j < nx; ++j) gain[((size_t)b * nu + c) * nx + j] = dz[((size_t)b * nx + j) * n + (size_t)nx * nn + (size_t)nu * (nn - 1) + c];
+    return PMPC_OK;
+}
+pmpc_status pmpc_mpc_batch_set_lineariser(pmpc_mpc_batch* h, pmpc_lin_dev_fn lin_fn) {
+    if (!h || (h->solve.fn != nullptr) != (lin_fn != nullptr)) return PMPC_ERR_INVALID_ARGUMENT;
+    h->lin_fn = lin_fn;
     return PMPC_OK;
 }
 pmpc_status pmpc_mpc_batch_update(pmpc_mpc_batch* h, const double* d, const double* lbx, const double* ubx, const double* lbg, const double* ubg) {

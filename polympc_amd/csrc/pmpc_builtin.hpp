@@ -38,16 +38,8 @@ template <class Model>
 pmpc_status linearise_dev_impl(pmpc_context* ctx, int P, int S, double t0, double tf, const double* mp, int nmp, int B,
                                const double* var, const double* d, const double* lam, double* cost, double* constr, double* jac,
                                double* cost_grad, double* lag_grad, double* lag_hess) {
-    const ChebData* cd = nullptr;
-    pmpc_status st = get_cheb(ctx, P, S, t0, tf, &cd);
-    if (st != PMPC_OK) return st;
-    const size_t lds = linearise_kernel_lds_bytes<Model>(P, S);
-    if (lds > ctx->lds_limit) return PMPC_ERR_UNSUPPORTED_SIZE;
-    HIPCHK(hipFuncSetAttribute((const void*)linearise_kernel<Model>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    Model mdl = make_model<Model>(mp, nmp);
-    hipLaunchKernelGGL(linearise_kernel<Model>, dim3(B), dim3(WAVE), lds, ctx->stream, mdl, cd, B, var, d, lam, cost, constr, jac, cost_grad, lag_grad, lag_hess);
-    HIPCHK(hipGetLastError());
-    return PMPC_OK;
+    const Model mdl = make_model<Model>(mp, nmp);
+    return pmpc::linearise_launch_dev<Model>(ctx, mdl, P, S, t0, tf, B, var, d, lam, cost, constr, jac, cost_grad, lag_grad, lag_hess);
 }
 
 template <class Model>

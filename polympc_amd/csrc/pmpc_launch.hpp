@@ -962,4 +962,20 @@ inline pmpc_status sqp_launch_dev(pmpc_context* ctx, const Model& mdl, int P, in
     return launch_sqp_plan(ctx, plan, a);
 }
 
+// Launch linearise_kernel for `Model` on DEVICE buffers, every output given (cost: 2 per instance; lam null = zeros), asynchronous on the context's
+// stream: pmpc_lin_dev_fn of the built-in models (linearise_dev_impl, pmpc_builtin.hpp) and of PMPC_REGISTER_OCP. It asks the context for no workspace.
+template <class Model>
+inline pmpc_status linearise_launch_dev(pmpc_context* ctx, const Model& mdl, int P, int S, double t0, double tf, int B, const double* var, const double* d,
+                                        const double* lam, double* cost, double* constr, double* jac, double* cost_grad, double* lag_grad, double* lag_hess) {
+    const void* cdv = nullptr; double* ws = nullptr; void* streamv = nullptr; size_t lds_limit = 0; unsigned long long* phase = nullptr; int force_lds = 0;
+    const pmpc_status st = pmpc_internal_services(ctx, P, S, t0, tf, 0, &cdv, &ws, &streamv, &lds_limit, &phase, &force_lds);
+    if (st != PMPC_OK) return st;
+    const size_t lds = linearise_kernel_lds_bytes<Model>(P, S);
+    if (lds > lds_limit) return PMPC_ERR_UNSUPPORTED_SIZE;
+    if (!set_lds_attr(linearise_kernel<Model>, lds)) return PMPC_ERR_HIP;
+    hipLaunchKernelGGL(linearise_kernel<Model>, dim3(B), dim3(WAVE), lds, (hipStream_t)streamv, mdl, (const ChebData*)cdv, B, var, d, lam, cost, constr, jac,
+                       cost_grad, lag_grad, lag_hess);
+    return launch_status();
+}
+
 }  // namespace pmpc
